@@ -15,6 +15,12 @@ whole-job aggregate QPS over all ranks.
 Driver contract: `python bench.py --gpus N --steps K --warmup W`; for N>1
 launched under torch.distributed.run with one rank per GPU over RCCL.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.
+`--dump-outputs DIR` also writes the last timed step's retrieval results as
+DIR/<name>.npy (same arguments → same corpus, weights and queries, and the
+same values up to rounding, so two builds can be compared output for
+output); `--full` is where any further measurement goes.
 """
 
 from __future__ import annotations
@@ -70,6 +76,15 @@ def parse_args():
                    help="tensor-parallel degree for the generator "
                         "(must equal world size; config #5: --model "
                         "llama3-70b --tp 8)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's "
+                        "retrieval results (query embeddings; dense, "
+                        "sparse and fused top-k scores) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements "
+                        "(everything beyond the headline figure belongs "
+                        "here; there is none at present — the stage "
+                        "breakdown on stderr costs no run of its own)")
     return p.parse_args()
 
 
@@ -95,12 +110,42 @@ class SyntheticCorpus:
                         metadata={"source": f"doc-{ref}"}, id=ref)
 
 
+def _zipf_terms(nnz: int, a: float, vocab: int, gen: torch.Generator,
+                device: str) -> torch.Tensor:
+    """nnz draws of (Zipf(a) - 1) % vocab as int64 on `device`: the rejection
+    sampler of Devroye (Non-Uniform Random Variate Generation, X.6.1 — the
+    one numpy's zipf uses), run on whole tensors.  Seeded by `gen`, so the
+    same arguments give the same draws."""
+    am1 = a - 1.0
+    b = 2.0 ** am1
+    out = torch.empty(nnz, dtype=torch.int64, device=device)
+    filled = 0
+    while filled < nnz:
+        n = min(int((nnz - filled) * 1.25) + 4096, 1 << 26)
+        u = 1.0 - torch.rand(n, generator=gen, device=device,
+                             dtype=torch.float64)          # (0, 1]
+        v = torch.rand(n, generator=gen, device=device, dtype=torch.float64)
+        x = torch.floor(u.pow(-1.0 / am1))
+        t = (1.0 + 1.0 / x).pow(am1)
+        ok = (x >= 1.0) & (x < 2.0 ** 63) & (v * x * (t - 1.0) / (b - 1.0)
+                                             <= t / b)
+        acc = x[ok][: nnz - filled]
+        out[filled: filled + acc.numel()] = torch.fmod(acc - 1.0, vocab).long()
+        filled += acc.numel()
+    return out
+
+
 def build_synthetic_indexes(n_docs: int, dim: int, vocab: int, device: str,
                             rank: int):
     """Dense: random unit vectors in HBM.  BM25: synthetic CSR postings
-    (zipf-ish doc frequencies) built directly on device-compatible arrays."""
-    g = torch.Generator(device="cpu")
-    g.manual_seed(1000 + rank)
+    (zipf-ish doc frequencies) drawn, sorted and kept on `device` — at 10M
+    docs the 200M postings took most of a minute to draw and sort on the
+    host, all of it outside the timed steps."""
+    # same corpus every run: the dense fill draws from the default
+    # generator, the postings from their own
+    torch.manual_seed(1000 + rank)
+    g = torch.Generator(device=device)
+    g.manual_seed(2000 + rank)
     dense = DenseIndex(dim=dim, device=device,
                        dtype=torch.float16 if device != "cpu" else torch.float32)
     # bulk vector fill without Document objects (payloads are synthetic)
@@ -117,27 +162,37 @@ def build_synthetic_indexes(n_docs: int, dim: int, vocab: int, device: str,
     # BM25 postings: ~20 distinct terms per doc
     per_doc = 20
     nnz = n_docs * per_doc
-    rng = np.random.RandomState(2000 + rank)
-    # zipf-flavored term draw, clipped to vocab
-    terms = (rng.zipf(1.3, size=nnz) - 1) % vocab
-    docs = np.repeat(np.arange(n_docs, dtype=np.int32), per_doc)
-    order = np.argsort(terms, kind="stable")
-    terms_sorted = terms[order]
-    post_doc = docs[order]
-    post_tf = (rng.randint(1, 5, size=nnz)).astype(np.float32)
-    counts = np.bincount(terms_sorted, minlength=vocab)
-    indptr = np.zeros(vocab + 1, np.int64)
-    np.cumsum(counts, out=indptr[1:])
+    # zipf-flavored term draw, clipped to vocab; posting p of the unsorted
+    # draw belongs to doc p // per_doc
+    terms = _zipf_terms(nnz, 1.3, vocab, g, device)
+    terms_sorted, order = torch.sort(terms, stable=True)
+    del terms
+    post_doc = (order // per_doc).to(torch.int32)
+    del order
+    post_tf = torch.randint(1, 5, (nnz,), generator=g,
+                            device=device).to(torch.float32)
+    counts = torch.bincount(terms_sorted, minlength=vocab)
+    del terms_sorted
+    indptr = torch.zeros(vocab + 1, dtype=torch.int64, device=device)
+    indptr[1:] = torch.cumsum(counts, 0)
+    doc_len = torch.randint(40, 200, (n_docs,), generator=g,
+                            device=device).to(torch.float32)
+    df = counts.to(torch.float64)
+    idf = torch.log((n_docs - df + 0.5) / (df + 0.5) + 1.0).to(torch.float32)
 
     bm = BM25Index()
     bm.doc_ids = None
-    bm.doc_len = rng.randint(40, 200, size=n_docs).astype(np.float32)
     bm.vocab = {f"term{i}": i for i in range(vocab)}
-    bm.indptr = indptr
-    bm.post_doc = post_doc
-    bm.post_tf = post_tf
-    df = counts.astype(np.float64)
-    bm.idf = np.log((n_docs - df + 0.5) / (df + 0.5) + 1.0).astype(np.float32)
+    bm.doc_len = doc_len.cpu().numpy()
+    bm.indptr = indptr.cpu().numpy()
+    bm.post_doc = post_doc.cpu().numpy()
+    bm.post_tf = post_tf.cpu().numpy()
+    bm.idf = idf.cpu().numpy()
+    if device != "cpu":
+        # already resident: no second upload at the first search
+        bm._device_arrays = {"indptr": indptr, "post_doc": post_doc,
+                             "post_tf": post_tf, "idf": idf,
+                             "doc_len": doc_len}
     return dense, bm
 
 
@@ -206,6 +261,33 @@ def bm25_search_batch(bm: BM25Index, term_id_lists: list[np.ndarray], k: int,
             idx.long().masked_fill(dead, -1))
 
 
+def dump_outputs(directory: str, last_out: dict) -> None:
+    """Write the last step's retrieval results, one DIR/<name>.npy each
+    (float32, shapes fixed by the arguments): the query embeddings, each
+    query's dense and sparse top-k scores (descending; 0 where BM25 found
+    fewer than k hits) and its fused top-k scores.
+
+    Only what repeats from run to run up to rounding is written.  The
+    step's retrieval overlaps the previous step's generation, and under
+    that contention the library GEMMs' accumulation order is not fixed, so
+    scores move in their last bits; the score VALUES written here follow
+    continuously, but ids flip at near-ties, and with them the rerank
+    candidates, sources and prompts.  Generated text is further out of
+    reach: the decode kernels accumulate through atomics and their GEMM
+    algorithm is picked by timing, and sampled decoding from random-init
+    weights turns a last-bit difference into another token."""
+    os.makedirs(directory, exist_ok=True)
+    sparse = last_out["sparse_scores"].float()
+    arrays = {
+        "query_embeddings": last_out["query_embeddings"].float(),
+        "dense_scores": last_out["dense_scores"].float(),
+        "sparse_scores": sparse.masked_fill(torch.isinf(sparse), 0.0),
+        "fused_scores": last_out["fused_scores"].float(),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     args = parse_args()
     rank, world = D.init_distributed()
@@ -266,6 +348,7 @@ def main():
         return out
 
     stage_t: dict[str, float] = {}
+    last_out: dict = {}     # --dump-outputs: what the latest step returned
 
     def _mark(name: str, t0: float) -> float:
         """Accumulate per-stage wall time for the stderr breakdown.  Syncs
@@ -409,6 +492,10 @@ def main():
             prompts.append(builder.system_prompt() + "\n\n" +
                            builder.build_qa_prompt(queries[qi], ctx))
         t0 = _mark("select", t0)
+        if args.dump_outputs:
+            # references only — converted after the timed region
+            last_out.update(query_embeddings=qv, dense_scores=d_scores,
+                            sparse_scores=s_scores, fused_scores=f_scores)
         return queries, reranked, prompts
 
     ret_stream = torch.cuda.Stream() if on_gpu else None
@@ -503,6 +590,9 @@ def main():
 
         tdist.all_reduce(e, op=tdist.ReduceOp.MAX)
     elapsed = float(e.item())
+
+    if args.dump_outputs and rank == 0 and last_out:
+        dump_outputs(args.dump_outputs, last_out)
 
     total_requests = args.batch * args.steps * (1 if tp_mode else world)
     qps = total_requests / elapsed

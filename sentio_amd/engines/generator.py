@@ -80,7 +80,10 @@ class _DecodeSession:
         # must not invalidate this capture — global/thread_local modes abort
         # on foreign allocator calls; the captured region itself only
         # contains this stream's decode ops
-        with torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
+        from sentio_amd.engines.graphed import capture_gc_guard
+
+        with capture_gc_guard(), \
+                torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
             self.static_logits = model.decode_step(self.static_tok, self.cache)
         self.cache.seq_lens.copy_(saved)
 

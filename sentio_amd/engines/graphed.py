@@ -14,6 +14,8 @@ reference src/core/embeddings/providers/jina.py:165)."""
 
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 import threading
 from typing import Callable
@@ -25,6 +27,40 @@ def graphs_enabled(device: str) -> bool:
     return (device != "cpu"
             and os.environ.get("SENTIO_DISABLE_HIPGRAPH", "0") != "1"
             and torch.cuda.is_available())
+
+
+_gc_lock = threading.Lock()
+_gc_depth = 0
+_gc_was_enabled = False
+
+
+@contextlib.contextmanager
+def capture_gc_guard():
+    """Keep Python's cyclic GC out of a hipGraph capture.
+
+    A dead engine is a reference cycle (engine <-> decode session) that
+    owns CUDAGraph objects, so only the cyclic collector frees it — at an
+    allocation count nobody controls.  If that lands inside a capture, the
+    CUDAGraph destructor runs there; on ROCm it synchronizes the device,
+    which is illegal while a stream is capturing, and the error thrown from
+    the destructor aborts the process.  torch.cuda.graph no longer collects
+    before capturing, so: collect dead cycles now (outside the capture),
+    then hold automatic collection off until the capture has ended.
+    Re-entrant across threads (captures on two threads may overlap)."""
+    global _gc_depth, _gc_was_enabled
+    with _gc_lock:
+        if _gc_depth == 0:
+            _gc_was_enabled = gc.isenabled()
+            gc.collect()
+            gc.disable()
+        _gc_depth += 1
+    try:
+        yield
+    finally:
+        with _gc_lock:
+            _gc_depth -= 1
+            if _gc_depth == 0 and _gc_was_enabled:
+                gc.enable()
 
 
 def bucket_batch(b: int, buckets=(1, 2, 4, 8, 16, 32, 64)) -> int:
@@ -57,7 +93,8 @@ class GraphedForward:
         self.graph = torch.cuda.CUDAGraph()
         # relaxed: see generator._capture — cross-thread engine work
         # (decode on the main thread) must not invalidate this capture
-        with torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
+        with capture_gc_guard(), \
+                torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
             self.out = self.fn(self.tokens, self.kv_lens)
 
     def run(self, tokens: torch.Tensor, kv_lens: torch.Tensor) -> torch.Tensor:

@@ -244,3 +244,37 @@ def test_encoder_stats_counters():
     assert s["cache_hits"] == 1
     assert s["errors"] == 0
     assert s["avg_time_ms_per_text"] > 0
+
+
+def test_capture_gc_guard_holds_cyclic_gc_off_and_restores():
+    """Inside the guard the cyclic collector is off (dead engine cycles were
+    collected on entry, none can be freed mid-capture); nesting keeps it off
+    until the outermost guard ends; the prior state comes back."""
+    import gc
+    import weakref
+
+    from sentio_amd.engines.graphed import capture_gc_guard
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a          # a dead cycle once the names go
+    ref = weakref.ref(a)
+    del a, b
+    assert gc.isenabled()
+    with capture_gc_guard():
+        assert ref() is None         # collected on entry
+        assert not gc.isenabled()
+        with capture_gc_guard():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+    assert gc.isenabled()
+
+    gc.disable()
+    try:
+        with capture_gc_guard():
+            assert not gc.isenabled()
+        assert not gc.isenabled()    # was off before: stays off
+    finally:
+        gc.enable()
