@@ -17,6 +17,13 @@ app.add_typer(api_app, name="api")
 app.add_typer(bench_app, name="bench")
 
 
+def _positive_top_p(value):
+    """--top-p takes (0, 1], the API's range."""
+    if value is not None and value <= 0.0:
+        raise typer.BadParameter("must be in (0, 1]")
+    return value
+
+
 @ingest_app.command("directory")
 def ingest_directory_cmd(
     path: str = typer.Argument(..., help="Directory of documents"),
@@ -84,19 +91,48 @@ def index_load(directory: str = typer.Argument(...)):
     typer.echo(json.dumps(get_container().load_indexes(directory), indent=2))
 
 
+def apply_sampling_defaults(settings, top_p, sampling_top_k, seed) -> None:
+    """CLI flags override the GEN_TOP_P / GEN_TOP_K service defaults."""
+    if top_p is not None:
+        settings.gen_top_p = float(top_p)
+    if sampling_top_k is not None:
+        settings.gen_top_k = int(sampling_top_k)
+    if seed is not None:
+        settings.gen_seed = int(seed)
+
+
 @app.command("chat")
-def chat_once(question: str = typer.Argument(...)):
+def chat_once(
+    question: str = typer.Argument(...),
+    top_p: float = typer.Option(None, "--top-p", min=0.0, max=1.0,
+                                callback=_positive_top_p,
+                                help="Nucleus mass (1.0 = off)"),
+    sampling_top_k: int = typer.Option(None, "--sampling-top-k", min=0,
+                                       help="Sampling top-k (0 = off)"),
+    seed: int = typer.Option(None, "--seed", min=0,
+                             help="Seed that reproduces the answer"),
+):
     from sentio_amd.serving.container import get_container
     from sentio_amd.serving.handlers import ChatHandler
 
     c = get_container()
     c.initialize_all()
-    result = ChatHandler(c).process(question)
+    result = ChatHandler(c).process(question, top_p=top_p,
+                                    sampling_top_k=sampling_top_k, seed=seed)
     typer.echo(json.dumps(result, indent=2))
 
 
 @app.command("run")
-def run_all(host: str = typer.Option(None), port: int = typer.Option(None)):
+def run_all(
+    host: str = typer.Option(None), port: int = typer.Option(None),
+    top_p: float = typer.Option(None, "--top-p", min=0.0, max=1.0,
+                                callback=_positive_top_p,
+                                help="Service-wide nucleus mass default"),
+    sampling_top_k: int = typer.Option(None, "--sampling-top-k", min=0,
+                                       help="Service-wide sampling top-k"),
+    seed: int = typer.Option(None, "--seed", min=0,
+                             help="Pin every request's sampling seed"),
+):
     """Start the full stack: API server (the built-in /ui page is the UI —
     reference `sentio run all` spawned API + Streamlit + Qdrant docker;
     here everything is in-process)."""
@@ -104,6 +140,8 @@ def run_all(host: str = typer.Option(None), port: int = typer.Option(None)):
 
     from sentio_amd.config import settings
     from sentio_amd.serving.app import create_app
+
+    apply_sampling_defaults(settings, top_p, sampling_top_k, seed)
 
     resolved_port = port or settings.api_port
     typer.echo(f"serving API + UI on http://{host or settings.api_host}:"

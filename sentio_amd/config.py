@@ -68,6 +68,9 @@ class Settings:
     generation_mode: str = "balanced"       # fast | balanced | quality | creative
     llm_max_tokens: int = 1024
     verifier_max_tokens: int = 512
+    gen_top_p: float = 1.0                  # nucleus mass; 1.0 = off
+    gen_top_k: int = 0                      # sampling top-k; 0 = off
+    gen_seed: int = -1                      # >= 0: seed of requests that set none
 
     # --- chunking / ingest (reference settings.py:89-90) ---
     chunk_size: int = 512
@@ -132,6 +135,9 @@ class Settings:
         "bm25_b": "BM25_B",
         "generation_mode": "GENERATION_MODE",
         "llm_max_tokens": "LLM_MAX_TOKENS",
+        "gen_top_p": "GEN_TOP_P",
+        "gen_top_k": "GEN_TOP_K",
+        "gen_seed": "GEN_SEED",
         "chunk_size": "CHUNK_SIZE",
         "chunk_overlap": "CHUNK_OVERLAP",
         "api_host": "API_HOST",

@@ -11,6 +11,7 @@ Temperature-per-mode mirrors reference generator.py:262-267
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Callable, Iterator
 
 import torch
@@ -22,6 +23,24 @@ from sentio_amd.engines.tokenizer import EOS_ID
 from sentio_amd.engines.transformer import KVCache, Transformer
 
 MODE_TEMPERATURE = {"fast": 0.0, "balanced": 0.3, "quality": 0.2, "creative": 0.7}
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """Per-request sampling controls.  top_k = 0 and top_p = 1.0 switch the
+    filters off; seed = None lets the engine derive one."""
+
+    temperature: float = 0.3
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int | None = None
+
+    @property
+    def filtered(self) -> bool:
+        """True when the request needs the per-row nucleus kernel
+        (ops.sample_filtered) instead of the default sampling path."""
+        return (int(self.top_k or 0) > 0 or float(self.top_p) < 1.0
+                or self.seed is not None)
 
 
 class _DecodeSession:
@@ -109,6 +128,7 @@ class GeneratorEngine:
         self.model = Transformer(self.cfg, device=device, dtype=dtype,
                                  seed=seed, tp=tp)
         self._step_seed = 0
+        self._derived_seeds = 0     # derive_seed()'s own counter
         import threading
 
         self._gen_lock = threading.Lock()   # decode sessions hold static state
@@ -310,11 +330,19 @@ class GeneratorEngine:
         temperature: float = 0.3,
         stop_on_eos: bool = True,
         on_token: Callable[[int, list[int]], None] | None = None,
+        top_k: int = 0,
+        top_p: float = 1.0,
+        seed: int | None = None,
     ) -> list[str]:
         """Batched generation.  Returns decoded completions (prompt excluded).
 
         on_token(step, token_ids_per_batch) fires after every decode step —
         the serving layer turns it into SSE streaming.
+
+        top_k / top_p / seed at their defaults keep the scalar-temperature
+        path (ops.sample_token).  Otherwise every step samples through
+        ops.sample_filtered; prompt i draws with seed + i, so a seeded
+        request reproduces its text whatever else shares the engine.
         """
         if not prompts:
             return []
@@ -328,9 +356,10 @@ class GeneratorEngine:
         self._gen_lock.acquire()
         try:
             with get_timer("generate").measure():
-                return self._generate_locked(prompts, max_new_tokens,
-                                             temperature, stop_on_eos,
-                                             on_token, _time)
+                return self._generate_locked(
+                    prompts, max_new_tokens, temperature, stop_on_eos,
+                    on_token, _time,
+                    SamplingParams(temperature, top_k, top_p, seed))
         finally:
             self._gen_lock.release()
 
@@ -348,7 +377,8 @@ class GeneratorEngine:
         return b
 
     def _generate_locked(self, prompts, max_new_tokens, temperature,
-                         stop_on_eos, on_token, _time) -> list[str]:
+                         stop_on_eos, on_token, _time,
+                         sampling: SamplingParams | None = None) -> list[str]:
         B_req = len(prompts)
         if self.device != "cpu":
             pad = self._bucket_batch(B_req) - B_req
@@ -395,7 +425,8 @@ class GeneratorEngine:
         # (every 16 steps) or the streaming callback — not per token.
         toks_buf = torch.zeros(B, max_new_tokens, dtype=torch.int64,
                                device=self.device)
-        cur = self._sample(logits, temperature)
+        sampler = self._make_sampler(sampling, temperature, B)
+        cur = sampler(logits, 0)
         n_steps = max_new_tokens
         for step in range(max_new_tokens):
             toks_buf[:, step] = cur
@@ -409,7 +440,7 @@ class GeneratorEngine:
             if step == max_new_tokens - 1:
                 break
             logits = sess.decode_step(cur)
-            cur = self._sample(logits, temperature)
+            cur = sampler(logits, step + 1)
         if self.device != "cpu":
             torch.cuda.synchronize()
         self.last_decode_s = _time.perf_counter() - _t0
@@ -438,24 +469,61 @@ class GeneratorEngine:
         self._step_seed += 1
         return ops.sample_token(logits, temperature, seed=self._step_seed)
 
+    def derive_seed(self) -> int:
+        """Seed for a filtered request that did not bring one."""
+        # its own counter: _step_seed feeds the default path's sample_token
+        # seeds, which filtered requests must not perturb
+        n = self._derived_seeds = self._derived_seeds + 1
+        return (n * 0x9E3779B1 + 909) & 0x7FFFFFFF
+
+    def _make_sampler(self, sampling: SamplingParams | None,
+                      temperature: float, batch: int):
+        """sampler(logits, step) for one generate/stream call.  Default
+        parameters: the present path (_sample -> ops.sample_token, same
+        seeds, same tokens).  Otherwise ops.sample_filtered with per-row
+        arrays built once; only the step counter changes per token."""
+        if sampling is None or not sampling.filtered:
+            return lambda logits, _step: self._sample(logits, temperature)
+        dev = self.device
+        base = sampling.seed if sampling.seed is not None \
+            else self.derive_seed()
+        temps = torch.full((batch,), float(sampling.temperature), device=dev)
+        ks = torch.full((batch,), int(sampling.top_k or 0), dtype=torch.int32,
+                        device=dev)
+        ps = torch.full((batch,), float(sampling.top_p), device=dev)
+        seeds = int(base) + torch.arange(batch, dtype=torch.int64, device=dev)
+
+        def sampler(logits, step):
+            steps = torch.full((batch,), int(step), dtype=torch.int32,
+                               device=dev)
+            return ops.sample_filtered(logits, temps, ks, ps, seeds, steps)
+
+        return sampler
+
     @torch.inference_mode()
     def stream(self, prompt: str, max_new_tokens: int = 128,
-               temperature: float = 0.3) -> Iterator[str]:
+               temperature: float = 0.3, top_k: int = 0, top_p: float = 1.0,
+               seed: int | None = None) -> Iterator[str]:
         """Yield text deltas token-by-token (single prompt) — the on-device
         equivalent of the reference's SSE streaming (openai.py:149-157).
         Holds the generation lock for the stream's duration (decode sessions
         and the model's decode-attention selection are engine-level state)."""
         with self._gen_lock:
-            yield from self._stream_locked(prompt, max_new_tokens, temperature)
+            yield from self._stream_locked(prompt, max_new_tokens, temperature,
+                                           top_k, top_p, seed)
 
     def _stream_locked(self, prompt: str, max_new_tokens: int,
-                       temperature: float) -> Iterator[str]:
+                       temperature: float, top_k: int = 0,
+                       top_p: float = 1.0,
+                       seed: int | None = None) -> Iterator[str]:
         prompt_budget = self.max_seq - max_new_tokens - 1
         ids = self.tokenizer.encode(prompt[-4 * prompt_budget:], prompt_budget)
         tokens = torch.tensor([ids], dtype=torch.int64, device=self.device)
         sess = self._decode_session(1, self.max_seq)
         logits = sess.prefill(tokens)
-        cur = self._sample(logits, temperature)
+        sampler = self._make_sampler(
+            SamplingParams(temperature, top_k, top_p, seed), temperature, 1)
+        cur = sampler(logits, 0)
         generated: list[int] = []
         emitted = ""
         for step in range(max_new_tokens):
@@ -471,4 +539,4 @@ class GeneratorEngine:
             if step == max_new_tokens - 1:
                 break
             logits = sess.decode_step(cur)
-            cur = self._sample(logits, temperature)
+            cur = sampler(logits, step + 1)

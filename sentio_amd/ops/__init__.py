@@ -269,6 +269,54 @@ def sample_token(logits, temperature: float, seed: int = 0):
     return torch_ref.sample_token(logits, temperature, g)
 
 
+def _row_tensor(v, B: int, dtype, device):
+    """Scalar or [B] -> contiguous [B] tensor of dtype on device."""
+    t = v if isinstance(v, torch.Tensor) else torch.tensor(v)
+    t = t.to(device=device, dtype=dtype).flatten()
+    if t.numel() == 1:
+        t = t.expand(B)
+    if t.numel() != B:
+        raise ValueError(f"per-row sampling parameter has {t.numel()} "
+                         f"entries for {B} rows")
+    return t.contiguous()
+
+
+def sample_support(logits, temperature, top_k, top_p):
+    """Deterministic half of filtered sampling: per row the threshold logit
+    tau and the size of the kept set {v : logit_v >= tau} after top-k then
+    top-p (renormalised over the top-k survivors; every token tied with tau
+    is kept).  logits [B, V]; parameters are [B] or scalars.  Returns
+    (tau [B] f32, count [B] i32); count is unspecified for greedy rows."""
+    B, dev = logits.shape[0], logits.device
+    t = _row_tensor(temperature, B, torch.float32, dev)
+    k = _row_tensor(top_k, B, torch.int32, dev)
+    p = _row_tensor(top_p, B, torch.float32, dev)
+    if _on_gpu(logits):
+        tau, count = _require_hip().sample_support(logits.contiguous(),
+                                                   t, k, p)
+        return tau, count
+    return torch_ref.sample_support(logits, t, k, p)
+
+
+def sample_filtered(logits, temperature, top_k, top_p, seed, step):
+    """Per-row temperature / top-k / top-p sampling with per-row seeds.
+    The noise for (row, v) is a counter hash of (seed_b, step_b, v): the same
+    (logits row, parameters, seed, step) gives the same token at any row
+    position and batch size.  logits [B, V]; the rest [B] or scalars.
+    Returns [B] int64.  CPU and GPU agree on the support and on greedy rows,
+    not on the stochastic pick."""
+    B, dev = logits.shape[0], logits.device
+    t = _row_tensor(temperature, B, torch.float32, dev)
+    k = _row_tensor(top_k, B, torch.int32, dev)
+    p = _row_tensor(top_p, B, torch.float32, dev)
+    sd = _row_tensor(seed, B, torch.int64, dev)
+    st = _row_tensor(step, B, torch.int32, dev)
+    if _on_gpu(logits):
+        return _require_hip().sample_filtered(logits.contiguous(), t, k, p,
+                                              sd, st)
+    return torch_ref.sample_filtered(logits, t, k, p, sd, st)
+
+
 def skinny_gemm(x, w):
     """Skinny decode GEMM: x [M<=32, K] @ W^T with W stored [N, K] row-major
     (TN layout) → [M, N] bf16.  Streams W rows straight to MFMA A-fragments.
@@ -313,5 +361,5 @@ def gemm_bf16(a, b):
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
-    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
+    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -23,6 +23,12 @@ hipError_t sentio_mean_pool_l2norm(const void*, const unsigned char*, float*,
                                    int, int, int, hipStream_t);
 hipError_t sentio_sample(const float*, long*, float*, int*, int, int, float,
                          unsigned, hipStream_t);
+hipError_t sentio_sample_support(const float*, const float*, const int*,
+                                 const float*, float*, int*, long, int,
+                                 hipStream_t);
+hipError_t sentio_sample_filtered(const float*, const float*, const int*,
+                                  const float*, const long*, const int*, long*,
+                                  long, int, hipStream_t);
 hipError_t sentio_cosine_scores_f16(const void*, const void*, float*, long,
                                     int, int, hipStream_t);
 hipError_t sentio_cosine_scores_bf16(const void*, const void*, float*, long,
@@ -184,6 +190,56 @@ torch::Tensor sample_token(torch::Tensor logits, double temperature,
                           ws_val.data_ptr<float>(), ws_idx.data_ptr<int>(),
                           B, l.size(1), (float)temperature,
                           (unsigned)seed, stream()), "sample");
+  return out;
+}
+
+// per-row sampling parameters: [B] tensors on the logits' device
+torch::Tensor row_param(const torch::Tensor& t, const torch::Tensor& like,
+                        torch::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == like.size(0), name,
+              " must be [B]");
+  return t.to(like.device(), dt).contiguous();
+}
+
+std::vector<torch::Tensor> sample_support(torch::Tensor logits,
+                                          torch::Tensor temperature,
+                                          torch::Tensor top_k,
+                                          torch::Tensor top_p) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "logits must be [B,V] GPU");
+  auto l = logits.to(torch::kFloat).contiguous();
+  const long B = l.size(0);
+  TORCH_CHECK(B > 0 && l.size(1) > 0, "logits must be non-empty");
+  auto t = row_param(temperature, l, torch::kFloat, "temperature");
+  auto k = row_param(top_k, l, torch::kInt, "top_k");
+  auto p = row_param(top_p, l, torch::kFloat, "top_p");
+  auto tau = torch::empty({B}, l.options());
+  auto count = torch::empty({B}, l.options().dtype(torch::kInt));
+  check_hip(sentio_sample_support(l.data_ptr<float>(), t.data_ptr<float>(),
+                                  k.data_ptr<int>(), p.data_ptr<float>(),
+                                  tau.data_ptr<float>(), count.data_ptr<int>(),
+                                  B, l.size(1), stream()), "sample_support");
+  return {tau, count};
+}
+
+torch::Tensor sample_filtered(torch::Tensor logits, torch::Tensor temperature,
+                              torch::Tensor top_k, torch::Tensor top_p,
+                              torch::Tensor seed, torch::Tensor step) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "logits must be [B,V] GPU");
+  auto l = logits.to(torch::kFloat).contiguous();
+  const long B = l.size(0);
+  TORCH_CHECK(B > 0 && l.size(1) > 0, "logits must be non-empty");
+  auto t = row_param(temperature, l, torch::kFloat, "temperature");
+  auto k = row_param(top_k, l, torch::kInt, "top_k");
+  auto p = row_param(top_p, l, torch::kFloat, "top_p");
+  auto sd = row_param(seed, l, torch::kLong, "seed");
+  auto st = row_param(step, l, torch::kInt, "step");
+  auto out = torch::empty({B}, l.options().dtype(torch::kLong));
+  check_hip(sentio_sample_filtered(l.data_ptr<float>(), t.data_ptr<float>(),
+                                   k.data_ptr<int>(), p.data_ptr<float>(),
+                                   (const long*)sd.data_ptr<int64_t>(),
+                                   st.data_ptr<int>(),
+                                   (long*)out.data_ptr<int64_t>(), B,
+                                   l.size(1), stream()), "sample_filtered");
   return out;
 }
 
@@ -366,6 +422,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_lastdim", &softmax_lastdim);
   m.def("mean_pool_l2norm", &mean_pool_l2norm);
   m.def("sample_token", &sample_token);
+  m.def("sample_support", &sample_support);
+  m.def("sample_filtered", &sample_filtered);
   m.def("cosine_scores", &cosine_scores);
   m.def("bm25_score", &bm25_score);
   m.def("flash_attn", &flash_attn);

@@ -191,6 +191,99 @@ def sample_token(
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
+def sample_support_row(row: torch.Tensor, temperature: float, top_k: int,
+                       top_p: float) -> dict:
+    """Sort-based fp64 oracle for ONE row [V] of the top-k -> top-p support.
+
+    Kept set = {v : logit_v >= tau}.  T <= 0: greedy, tau = row max.  T > 0:
+    z = logit/T, p = softmax(z); -inf logits are dropped; 1 <= top_k < (number
+    of finite logits) keeps the top_k largest; top_p < 1 keeps the shortest
+    prefix of those whose cumulative mass reaches top_p * M_k (M_k = mass of
+    the top-k survivors), never fewer than one token; tau is the raw logit
+    of the last kept token and EVERY token tied with tau is kept.
+
+    Returns tau plus the sorted values / cumulative masses the tests use for
+    their margin conditions (`vals`, `cs` normalised by the total row mass,
+    `target` in the same unit, `n` the prefix length)."""
+    x = row.detach().cpu().to(torch.float64).flatten()
+    x = torch.where(torch.isnan(x), torch.full_like(x, -math.inf), x)
+    xmax = float(x.max())
+    if not (temperature > 0.0) or math.isinf(xmax):
+        return {"tau": xmax, "greedy": True}
+    vals = torch.sort(x[x > -math.inf], descending=True).values
+    w = torch.exp((vals - vals[0]) / float(temperature))
+    total = float(w.sum())
+    n = vals.numel()
+    if 1 <= top_k < n:
+        n = int(top_k)
+    cs = torch.cumsum(w, 0) / total
+    target = None
+    if top_p < 1.0:
+        target = float(top_p) * float(cs[n - 1])
+        idx = int(torch.searchsorted(cs[:n], torch.tensor(target,
+                                                          dtype=torch.float64)))
+        n = min(max(idx + 1, 1), n)
+    return {"tau": float(vals[n - 1]), "greedy": False, "vals": vals,
+            "cs": cs, "target": target, "n": n}
+
+
+def _row_params(B: int, temperature, top_k, top_p):
+    def bc(v, dtype):
+        t = torch.as_tensor(v).detach().cpu().to(dtype).flatten()
+        return t.expand(B) if t.numel() == 1 else t
+
+    return (bc(temperature, torch.float32), bc(top_k, torch.int64),
+            bc(top_p, torch.float32))
+
+
+def sample_support(logits: torch.Tensor, temperature, top_k, top_p):
+    """logits [B, V] -> (tau [B] f32, count [B] i32); see sample_support_row.
+    Parameters are per-row [B] (scalars broadcast) and read at fp32, like the
+    kernel reads them."""
+    x = logits.detach().cpu().float()
+    B = x.shape[0]
+    t, k, p = _row_params(B, temperature, top_k, top_p)
+    tau = torch.empty(B, dtype=torch.float32)
+    for b in range(B):
+        tau[b] = sample_support_row(x[b], float(t[b]), int(k[b]),
+                                    float(p[b]))["tau"]
+    xc = torch.where(torch.isnan(x), torch.full_like(x, -math.inf), x)
+    count = (xc >= tau[:, None]).sum(dim=1).to(torch.int32)
+    return tau, count
+
+
+def sample_filtered(logits: torch.Tensor, temperature, top_k, top_p, seed,
+                    step) -> torch.Tensor:
+    """logits [B, V] -> [B] int64: mask to the support, then one draw per row
+    from a generator seeded from (seed_b, step_b) alone -- a row's token does
+    not depend on its position or on B.  Greedy rows take the lowest index of
+    the maximum."""
+    x = logits.detach().cpu().float()
+    B = x.shape[0]
+    t, _, _ = _row_params(B, temperature, top_k, top_p)
+    sd = torch.as_tensor(seed).detach().cpu().to(torch.int64).flatten()
+    st = torch.as_tensor(step).detach().cpu().to(torch.int64).flatten()
+    sd = sd.expand(B) if sd.numel() == 1 else sd
+    st = st.expand(B) if st.numel() == 1 else st
+    tau, _ = sample_support(x, temperature, top_k, top_p)
+    out = torch.empty(B, dtype=torch.int64)
+    for b in range(B):
+        row = torch.where(torch.isnan(x[b]), torch.full_like(x[b], -math.inf),
+                          x[b])
+        T = float(t[b])
+        if not (T > 0.0) or math.isinf(float(row.max())):
+            out[b] = int(row.argmax())
+            continue
+        z = (row.double() - float(row.max())) / T
+        z = torch.where(row >= tau[b], z, torch.full_like(z, -math.inf))
+        g = torch.Generator(device="cpu")
+        g.manual_seed(((int(sd[b]) * 0x9E3779B1) ^ (int(st[b]) * 0x85EBCA6B
+                                                   + 0x27D4EB2F))
+                      & 0x7FFFFFFFFFFFFFFF)
+        out[b] = int(torch.multinomial(torch.softmax(z, 0), 1, generator=g))
+    return out
+
+
 def decode_qkv_prep(
     qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor

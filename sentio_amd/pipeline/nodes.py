@@ -137,6 +137,17 @@ def create_generator_node(generator, mode: str = "balanced",
             from sentio_amd.engines.generator import MODE_TEMPERATURE
 
             temperature = MODE_TEMPERATURE.get(mode, 0.3)
+        # nucleus sampling controls ride in the metadata; requests that set
+        # none of them call generate() exactly as before
+        meta = state.get("metadata", {})
+        sampling = {}
+        if isinstance(meta.get("top_p"), (int, float)) and meta["top_p"] < 1.0:
+            sampling["top_p"] = float(meta["top_p"])
+        if isinstance(meta.get("sampling_top_k"), int) \
+                and meta["sampling_top_k"] > 0:
+            sampling["top_k"] = int(meta["sampling_top_k"])
+        if isinstance(meta.get("seed"), int):
+            sampling["seed"] = int(meta["seed"])
         history = state.get("metadata", {}).get("history") or []
         hist_txt = "".join(
             f"{turn.get('role', 'user')}: {turn.get('content', '')}\n"
@@ -148,7 +159,8 @@ def create_generator_node(generator, mode: str = "balanced",
         prompt += builder.build_qa_prompt(state["query"], context, mode)
         try:
             answer = generator.generate(
-                [prompt], max_new_tokens=max_tokens, temperature=float(temperature)
+                [prompt], max_new_tokens=max_tokens,
+                temperature=float(temperature), **sampling
             )[0]
         except Exception as exc:
             logger.error("generation failed: %s", exc)

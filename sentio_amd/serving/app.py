@@ -62,6 +62,11 @@ class ChatRequest(BaseModel):
     history: list[dict[str, str]] | None = Field(default_factory=list)
     top_k: int | None = Field(default=3, ge=1, le=20)
     temperature: float | None = Field(default=0.7, ge=0.0, le=2.0)
+    # generator sampling controls (top_k above is the retrieval depth);
+    # unset fields take GEN_TOP_P / GEN_TOP_K
+    top_p: float | None = Field(default=None, gt=0.0, le=1.0)
+    sampling_top_k: int | None = Field(default=None, ge=0)   # 0 = off
+    seed: int | None = Field(default=None, ge=0)
 
     @field_validator("question")
     @classmethod
@@ -126,6 +131,8 @@ def create_app(settings: Settings | None = None,
         fe = container._cache.get("generator_frontend")
         if fe is not None and hasattr(fe, "batcher"):
             fe.batcher.stop()
+        if fe is not None and hasattr(fe, "sampled_batcher"):
+            fe.sampled_batcher.stop()
         for eng_key in ("encoder", "reranker"):
             micro = getattr(container._cache.get(eng_key), "micro", None)
             if micro is not None:
@@ -228,7 +235,8 @@ def create_app(settings: Settings | None = None,
         with metrics_collector.track_request("/chat"):
             t0 = time.perf_counter()
             result = await _run_sync(chat_handler.process, req.question,
-                                     req.top_k, req.temperature, req.history)
+                                     req.top_k, req.temperature, req.history,
+                                     req.top_p, req.sampling_top_k, req.seed)
             performance_monitor.record_value(
                 "chat_latency_ms", (time.perf_counter() - t0) * 1e3)
             return result
@@ -261,9 +269,15 @@ def create_app(settings: Settings | None = None,
             # abandoned/slow client (e.g. read timeout) leaks the lock and
             # wedges every later generation.  The batched frontend streams
             # from a per-request token queue instead.
+            from sentio_amd.serving.handlers import resolve_sampling
+
+            sampling = resolve_sampling(s, req.top_p, req.sampling_top_k,
+                                        req.seed)
+            if "sampling_top_k" in sampling:
+                sampling["top_k"] = sampling.pop("sampling_top_k")
             for delta in container.generator_frontend().stream(
                     prompt, max_new_tokens=s.llm_max_tokens,
-                    temperature=req.temperature or 0.3):
+                    temperature=req.temperature or 0.3, **sampling):
                 yield f"data: {delta}\n\n"
             yield "data: [DONE]\n\n"
 

@@ -15,7 +15,10 @@ Three coalescing layers live here:
   moment they finish — no wave barrier.
 * `DynamicBatcher` (CONTINUOUS_BATCHING=0 fallback, and the mock-engine
   path) — wave batching: group by sampling params, keep collecting while
-  the engine runs the previous batch, run ONE batched generate.
+  the engine runs the previous batch, run ONE batched generate.  It also
+  serves, beside the continuous loop, the requests that set top-k /
+  top-p / seed (`_SampledItem`): the slot loop samples with per-row
+  temperature only.
 * `MicroBatcher` + `BatchedEncoder`/`BatchedReranker` — concurrent
   single-query embeds / rerank pair scores coalesce into one engine
   forward each.
@@ -53,6 +56,53 @@ class _Item:
         return (self.temperature, self.max_new_tokens, self.stop_on_eos)
 
 
+@dataclass
+class _SampledItem(_Item):
+    """A request with nucleus-sampling controls (top-k / top-p / seed).
+    Only the wave batcher carries these; default requests stay plain
+    `_Item`s and group exactly as before."""
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int | None = None
+
+    @property
+    def sampling_kwargs(self) -> dict:
+        return {"top_k": self.top_k, "top_p": self.top_p, "seed": self.seed}
+
+    @property
+    def group_key(self) -> tuple:
+        # a wave draws prompt i with seed + i: a seeded request must sit at
+        # row 0 of its own wave to reproduce, so it never shares one
+        return (self.temperature, self.max_new_tokens, self.stop_on_eos,
+                self.top_k, self.top_p, self.seed,
+                id(self) if self.seed is not None else None)
+
+
+def _make_item(prompt: str, max_new_tokens: int, temperature: float,
+               stop_on_eos: bool, stream_q=None, top_k: int = 0,
+               top_p: float = 1.0, seed: int | None = None) -> _Item:
+    top_k, top_p = int(top_k or 0), float(top_p)
+    if top_k > 0 or top_p < 1.0 or seed is not None:
+        return _SampledItem(prompt, max_new_tokens, float(temperature),
+                            stop_on_eos, stream_q=stream_q, top_k=top_k,
+                            top_p=top_p, seed=seed)
+    return _Item(prompt, max_new_tokens, float(temperature), stop_on_eos,
+                 stream_q=stream_q)
+
+
+def _sampling_only(kwargs: dict) -> dict:
+    """The nucleus-sampling keywords of a frontend call (top_k / top_p /
+    seed) that switch a filter on; {} for a default request."""
+    out = {}
+    if int(kwargs.get("top_k") or 0) > 0:
+        out["top_k"] = int(kwargs["top_k"])
+    if kwargs.get("top_p") is not None and float(kwargs["top_p"]) < 1.0:
+        out["top_p"] = float(kwargs["top_p"])
+    if kwargs.get("seed") is not None:
+        out["seed"] = int(kwargs["seed"])
+    return out
+
+
 class DynamicBatcher:
     def __init__(self, generator, max_batch: int = 32,
                  max_wait_ms: float = 8.0):
@@ -68,22 +118,27 @@ class DynamicBatcher:
     # ----- caller side -----
     def generate(self, prompt: str, max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
-                 timeout_s: float = 300.0) -> str:
+                 timeout_s: float = 300.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: int | None = None) -> str:
         self.start()
-        item = _Item(prompt, max_new_tokens, float(temperature), stop_on_eos)
+        item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
+                          top_k=top_k, top_p=top_p, seed=seed)
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
 
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
-                        temperature: float = 0.3, timeout_s: float = 300.0):
+                        temperature: float = 0.3, timeout_s: float = 300.0,
+                        top_k: int = 0, top_p: float = 1.0,
+                        seed: int | None = None):
         """Yield text deltas token-by-token.  The request JOINS batched
         decode (continuous-batching-lite: it occupies a batch slot and its
         token ids stream out per decode step); concurrent non-stream chat
         requests coalesce into the same engine batches, so neither starves
         the other."""
         self.start()
-        item = _Item(prompt, max_new_tokens, float(temperature), True,
-                     stream_q=queue.Queue())
+        item = _make_item(prompt, max_new_tokens, temperature, True,
+                          stream_q=queue.Queue(), top_k=top_k, top_p=top_p,
+                          seed=seed)
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
 
@@ -193,6 +248,9 @@ class DynamicBatcher:
                 temperature=batch[0].temperature,
                 stop_on_eos=batch[0].stop_on_eos,
                 on_token=on_token,
+                # {} for default requests: generators that predate the
+                # sampling controls keep working
+                **getattr(batch[0], "sampling_kwargs", {}),
             )
             for it, out in zip(batch, outs):
                 if it.stream_q is not None:
@@ -536,6 +594,12 @@ class ContinuousGenerator:
     def __init__(self, raw, slots: int = 32):
         self.raw = raw
         self.batcher = ContinuousBatcher(raw, slots=slots)
+        # Requests with top-k / top-p / seed do not join the slot loop (it
+        # samples with per-row temperature only): they run as waves of the
+        # raw engine through a DynamicBatcher, like multi-prompt calls do.
+        # A wave holds the engine lock for its whole generation, the loop
+        # takes it per step: the loop stalls while a wave decodes.
+        self.sampled_batcher = DynamicBatcher(raw, max_batch=slots)
 
     def generate(self, prompts: list[str], max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
@@ -544,13 +608,24 @@ class ContinuousGenerator:
             return self.raw.generate(prompts, max_new_tokens=max_new_tokens,
                                      temperature=temperature,
                                      stop_on_eos=stop_on_eos, **kwargs)
+        sampling = _sampling_only(kwargs)
+        if sampling:
+            return [self.sampled_batcher.generate(
+                prompts[0], max_new_tokens=max_new_tokens,
+                temperature=temperature, stop_on_eos=stop_on_eos,
+                **sampling)]
         return [self.batcher.generate(prompts[0],
                                       max_new_tokens=max_new_tokens,
                                       temperature=temperature,
                                       stop_on_eos=stop_on_eos)]
 
     def stream(self, prompt: str, max_new_tokens: int = 128,
-               temperature: float = 0.3):
+               temperature: float = 0.3, **kwargs):
+        sampling = _sampling_only(kwargs)
+        if sampling:
+            return self.sampled_batcher.generate_stream(
+                prompt, max_new_tokens=max_new_tokens,
+                temperature=temperature, **sampling)
         return self.batcher.generate_stream(prompt,
                                             max_new_tokens=max_new_tokens,
                                             temperature=temperature)
@@ -743,15 +818,17 @@ class BatchedGenerator:
         return [self.batcher.generate(prompts[0],
                                       max_new_tokens=max_new_tokens,
                                       temperature=temperature,
-                                      stop_on_eos=stop_on_eos)]
+                                      stop_on_eos=stop_on_eos,
+                                      **_sampling_only(kwargs))]
 
     def stream(self, prompt: str, max_new_tokens: int = 128,
-               temperature: float = 0.3):
+               temperature: float = 0.3, **kwargs):
         """Streams JOIN batched decode via the DynamicBatcher — no request
         holds the engine's generation lock for its stream's lifetime."""
         return self.batcher.generate_stream(prompt,
                                             max_new_tokens=max_new_tokens,
-                                            temperature=temperature)
+                                            temperature=temperature,
+                                            **_sampling_only(kwargs))
 
     def __getattr__(self, name):
         return getattr(self.raw, name)

@@ -18,6 +18,28 @@ from sentio_amd.serving.container import ServiceContainer
 logger = logging.getLogger(__name__)
 
 
+def resolve_sampling(settings, top_p: float | None = None,
+                     sampling_top_k: int | None = None,
+                     seed: int | None = None) -> dict[str, Any]:
+    """Request-level nucleus sampling controls as pipeline metadata.  A field
+    the request leaves unset takes the service-wide default (GEN_TOP_P /
+    GEN_TOP_K); values that switch a filter off are dropped, so a request
+    with nothing set yields {} and stays on the default sampling path."""
+    p = top_p if top_p is not None else getattr(settings, "gen_top_p", 1.0)
+    k = sampling_top_k if sampling_top_k is not None \
+        else getattr(settings, "gen_top_k", 0)
+    if seed is None and getattr(settings, "gen_seed", -1) >= 0:
+        seed = settings.gen_seed
+    out: dict[str, Any] = {}
+    if p is not None and float(p) < 1.0:
+        out["top_p"] = float(p)
+    if k is not None and int(k) > 0:
+        out["sampling_top_k"] = int(k)
+    if seed is not None:
+        out["seed"] = int(seed)
+    return out
+
+
 class ChatHandler:
     def __init__(self, container: ServiceContainer):
         self.container = container
@@ -25,9 +47,16 @@ class ChatHandler:
 
     def process(self, question: str, top_k: int | None = None,
                 temperature: float | None = None,
-                history: list[dict[str, str]] | None = None) -> dict[str, Any]:
+                history: list[dict[str, str]] | None = None,
+                top_p: float | None = None,
+                sampling_top_k: int | None = None,
+                seed: int | None = None) -> dict[str, Any]:
+        """top_k is the RETRIEVAL depth; sampling_top_k / top_p / seed are
+        the generator's sampling controls."""
         query_id = str(uuid.uuid4())
         meta: dict[str, Any] = {"query_id": query_id}
+        meta.update(resolve_sampling(getattr(self.container, "settings", None), top_p,
+                                     sampling_top_k, seed))
         if top_k is not None:
             meta["user_top_k"] = int(top_k)
         if temperature is not None:

@@ -41,6 +41,8 @@ UI_HTML = """<!doctype html>
          oninput="document.getElementById('tval').textContent=this.value">
          <span id="tval">0.3</span></label>
   <label>top-k <input type="number" id="topk" min="1" max="50" value="10"></label>
+  <label>top-p <input type="number" id="topp" min="0.05" max="1" step="0.05" value="1"></label>
+  <label>sample-k <input type="number" id="sampk" min="0" max="1000" value="0"></label>
   <button onclick="ask()">Send</button>
   <button class="sec" onclick="clearChat()">Clear chat</button>
  </div>
@@ -98,6 +100,11 @@ async function ask(){
               temperature:+document.getElementById('temp').value,
               top_k:+document.getElementById('topk').value,
               history:history.slice(-8)};
+  // off values are omitted so the service defaults (GEN_TOP_P / GEN_TOP_K) apply
+  const tp=+document.getElementById('topp').value;
+  const sk=+document.getElementById('sampk').value;
+  if(tp>0&&tp<1)body.top_p=tp;
+  if(sk>0)body.sampling_top_k=sk;
   try{
     if(document.getElementById('stream').checked){
       const r=await fetch('/chat/stream',{method:'POST',

@@ -19,7 +19,8 @@ CSRC = ROOT / "sentio_amd" / "ops" / "csrc"
 OUT = ROOT / "sentio_amd" / "ops" / "_sentio_hip.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-KERNEL_TUS = ["elementwise.hip", "retrieval.hip", "attention.hip", "gemm.hip", "blaslt.hip"]
+KERNEL_TUS = ["elementwise.hip", "retrieval.hip", "attention.hip", "gemm.hip", "blaslt.hip",
+              "sampling.hip"]
 BINDING_TU = "bindings.hip"
 
 
