@@ -191,10 +191,12 @@ class GeneratorEngine:
     # seed changes per step).  Sessions are pooled by (batch, cache size).
     _GRAPHS_ENABLED = True
 
-    def _decode_session(self, batch: int, cache_len: int):
+    def _use_graphs(self) -> bool:
+        """Whether a NEW decode session captures its step into a hipGraph
+        (the environment is read here, at session creation)."""
         import os
 
-        use_graphs = (
+        return (
             self._GRAPHS_ENABLED
             and self.device != "cpu"
             # TP decode: the chunked async all-reduces (parallel/tp.py)
@@ -207,6 +209,8 @@ class GeneratorEngine:
                  or os.environ.get("SENTIO_TP_HIPGRAPH", "0") == "1")
             and os.environ.get("SENTIO_DISABLE_HIPGRAPH", "0") != "1"
         )
+
+    def _decode_session(self, batch: int, cache_len: int):
         key = (batch, cache_len)
         pool = getattr(self, "_sessions", None)
         if pool is None:
@@ -215,7 +219,7 @@ class GeneratorEngine:
             sess = pool[key]
             sess.cache.seq_lens.zero_()
             return sess
-        sess = _DecodeSession(self, batch, cache_len, use_graphs)
+        sess = _DecodeSession(self, batch, cache_len, self._use_graphs())
         pool[key] = sess
         return sess
 
@@ -224,16 +228,7 @@ class GeneratorEngine:
         """A PRIVATE decode session for the continuous batcher: its KV
         slots persist across requests, so it must never come from (or be
         reset by) the shared _decode_session pool."""
-        import os
-
-        use_graphs = (
-            self._GRAPHS_ENABLED
-            and self.device != "cpu"
-            and (not self.model.tp.enabled
-                 or os.environ.get("SENTIO_TP_HIPGRAPH", "0") == "1")
-            and os.environ.get("SENTIO_DISABLE_HIPGRAPH", "0") != "1"
-        )
-        return _DecodeSession(self, slots, self.max_seq, use_graphs)
+        return _DecodeSession(self, slots, self.max_seq, self._use_graphs())
 
     @torch.inference_mode()
     def prefill_admission(self, prompts: list[str],
@@ -506,8 +501,8 @@ class GeneratorEngine:
                seed: int | None = None) -> Iterator[str]:
         """Yield text deltas token-by-token (single prompt) — the on-device
         equivalent of the reference's SSE streaming (openai.py:149-157).
-        Holds the generation lock for the stream's duration (decode sessions
-        and the model's decode-attention selection are engine-level state)."""
+        Holds the generation lock for the stream's duration (the pooled
+        decode sessions are engine-level state)."""
         with self._gen_lock:
             yield from self._stream_locked(prompt, max_new_tokens, temperature,
                                            top_k, top_p, seed)

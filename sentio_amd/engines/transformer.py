@@ -20,6 +20,7 @@ src/core/rerankers/jina_reranker.py:172, src/core/llm/providers/openai.py:117).
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -147,6 +148,19 @@ class Transformer:
                                              cfg.rope_base, device)
         self.rope_cos, self.rope_sin = cos, sin
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        # Decode-attention implementation, fixed for the model's lifetime
+        # (forward_decode is captured into hipGraphs and prefill runs on the
+        # batcher's admission stream beside it, so nothing may reassign it).
+        # SENTIO_DECODE_ATTN=bmm selects the two-batched-GEMM formulation;
+        # anything else (auto, hand) the hand split-S kernel.  bmm looked
+        # ~1.4x faster in an isolated cold-box probe, but IN CONTEXT the
+        # extra P-matrix traffic + per-layer kernel tail made the end-to-end
+        # bench 7% slower (16.8 vs 18.1 QPS) — the hand kernel with fused
+        # online softmax is the default at any cache fill.
+        self.decode_attn = (
+            ops.decode_attention_bmm
+            if os.environ.get("SENTIO_DECODE_ATTN") == "bmm"
+            else ops.decode_attention)
 
     # ----- core blocks -----
     def _attn(self, x: torch.Tensor, layer: dict, pos: torch.Tensor,
@@ -245,38 +259,17 @@ class Transformer:
             normed, x = ops.rmsnorm_residual(f, x, w_next, eps)
         return normed
 
-    # Decode-attention path choice (env override SENTIO_DECODE_ATTN=hand|bmm):
-    # the bmm formulation looked ~1.4x faster in an isolated cold-box probe,
-    # but IN CONTEXT the extra P-matrix traffic + per-layer kernel tail made
-    # the end-to-end bench 7% slower (16.8 vs 18.1 QPS) — the hand split-S
-    # kernel with fused online softmax stays the default at any fill.
-    _BMM_FILL_THRESHOLD = 2.0   # auto never picks bmm
-
-    def _decode_attn_impl(self, fill_ratio: float):
-        import os
-
-        mode = os.environ.get("SENTIO_DECODE_ATTN", "auto")
-        if mode == "hand":
-            return ops.decode_attention
-        if mode == "bmm":
-            return ops.decode_attention_bmm
-        return (ops.decode_attention_bmm
-                if fill_ratio >= self._BMM_FILL_THRESHOLD
-                else ops.decode_attention)
-
     # ----- decode fast path: fused RoPE + KV-cache write + fused norms -----
     def _attn_decode(self, normed: torch.Tensor, layer: dict, cache: KVCache,
-                     layer_idx: int, attn_lens: torch.Tensor,
-                     attn_fn=None) -> torch.Tensor:
+                     layer_idx: int, attn_lens: torch.Tensor) -> torch.Tensor:
         B = normed.shape[0]
         d = self.cfg.dim
         hd = self.cfg.head_dim
         qkv = ops.lt_linear(normed.view(B, d), layer["wqkv"])
         q = ops.decode_qkv_prep(qkv, cache.k[layer_idx], cache.v[layer_idx],
                                 self.rope_cos, self.rope_sin, cache.seq_lens)
-        attn = attn_fn or ops.decode_attention
-        out = attn(q, cache.k[layer_idx], cache.v[layer_idx],
-                   attn_lens, self.scale)
+        out = self.decode_attn(q, cache.k[layer_idx], cache.v[layer_idx],
+                               attn_lens, self.scale)
         out = linear_row_parallel(out.view(B, self.h_local * hd),
                                   layer["wo"], self.tp, linear=ops.lt_linear)
         return out.view(B, 1, d)
@@ -291,14 +284,9 @@ class Transformer:
         layers = self.w.layers
         n = len(layers)
         attn_lens = cache.seq_lens + 1
-        # hand vs bmm kernel chosen at prefill time (set by the caller via
-        # self.decode_attn_fn — no device sync here: this path is captured
-        # into hipGraphs)
-        attn_fn = getattr(self, "decode_attn_fn", None)
         normed = ops.rmsnorm(x, layers[0]["attn_norm"], eps)
         for i, layer in enumerate(layers):
-            a = self._attn_decode(normed, layer, cache, i, attn_lens,
-                                  attn_fn=attn_fn)
+            a = self._attn_decode(normed, layer, cache, i, attn_lens)
             normed, x = ops.rmsnorm_residual(a, x, layer["ffn_norm"], eps)
             f = self._ffn(normed, layer)
             w_next = layers[i + 1]["attn_norm"] if i + 1 < n else self.w.final_norm
@@ -327,9 +315,8 @@ class Transformer:
         lens: per-row true prompt lengths for right-padded batches — masks
         pad keys out of attention, starts decode at each row's own length,
         and gathers logits at lens-1 (batch composition no longer changes a
-        request's output).  Also picks the decode-attention implementation
-        for the upcoming decode steps from the cache fill ratio (prompt
-        length is host-side here — no sync)."""
+        request's output).  Touches no model state: safe to run on a side
+        stream while decode replays."""
         B, S = tokens.shape
         lens_i = None if lens is None else lens.to(torch.int32)
         hidden = self.forward_hidden(tokens, cache=cache, kv_lens=lens_i)
@@ -339,9 +326,6 @@ class Transformer:
         else:
             cache.seq_lens.copy_(lens_i)
             last_idx = lens_i.long() - 1
-        if self.device != "cpu":
-            self.decode_attn_fn = self._decode_attn_impl(
-                S / max(cache.max_seq, 1))
         return self.logits(hidden, last_idx)
 
     def prefill_suffix(self, suffix_tokens: torch.Tensor, cache: KVCache,
@@ -364,11 +348,6 @@ class Transformer:
         else:
             cache.seq_lens.copy_(lens_abs)
             last_idx = suffix_lens.long() - 1
-        if self.device != "cpu":
-            self.decode_attn_fn = self._decode_attn_impl(
-                (prefix_len + S) / max(cache.max_seq, 1))
-        else:
-            self.decode_attn_fn = None
         return self.logits(hidden, last_idx)
 
     def decode_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:

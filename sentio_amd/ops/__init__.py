@@ -9,6 +9,8 @@ hermetic config).
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 from sentio_amd.ops import torch_ref
@@ -107,18 +109,20 @@ def softmax(x, dim: int = -1):
 
 # ---------------- attention ----------------
 
+def _attn_scale(q, scale: float | None) -> float:
+    """Softmax scale: the caller's, or 1/sqrt(head_dim)."""
+    return float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+
+
 def attention(q, k, v, causal: bool = True, scale: float | None = None,
               kv_lens=None):
     if _on_gpu(q):
-        import math
-
-        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         if kv_lens is None:
             kv_lens = torch.full((q.shape[0],), q.shape[1], dtype=torch.int32,
                                  device=q.device)
         return _require_hip().flash_attn(
             q.contiguous(), k.contiguous(), v.contiguous(), bool(causal),
-            float(s), kv_lens.to(torch.int32).contiguous()
+            _attn_scale(q, scale), kv_lens.to(torch.int32).contiguous()
         )
     return torch_ref.attention(q, k, v, causal, scale, kv_lens)
 
@@ -129,23 +133,19 @@ def attention_cache(q, k_cache, v_cache, kv_lens, q_off: int,
     cache (prefix-KV caching): q [B, S_suf, H, D] at absolute positions
     q_off..q_off+S_suf-1; caches [B, Hkv, Smax, D]; kv_lens [B] absolute
     valid lengths (prefix + suffix)."""
-    import math
-
-    s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    s = _attn_scale(q, scale)
     if _on_gpu(q):
         return _require_hip().flash_attn_cache(
             q.contiguous(), k_cache, v_cache,
-            kv_lens.to(torch.int32).contiguous(), float(s), int(q_off))
+            kv_lens.to(torch.int32).contiguous(), s, int(q_off))
     return torch_ref.attention_cache(q, k_cache, v_cache, kv_lens, q_off, s)
 
 
 def decode_attention(q, k_cache, v_cache, seq_lens, scale: float | None = None):
     if _on_gpu(q):
-        import math
-
-        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _require_hip().decode_attn(
-            q.contiguous(), k_cache, v_cache, seq_lens.contiguous(), float(s)
+            q.contiguous(), k_cache, v_cache, seq_lens.contiguous(),
+            _attn_scale(q, scale)
         )
     return torch_ref.decode_attention(q, k_cache, v_cache, seq_lens, scale)
 
@@ -160,14 +160,12 @@ def decode_attention_bmm(q, k_cache, v_cache, seq_lens,
     the hand kernel (ops.decode_attention) wins for mostly-empty caches.
     All ops are tensor-graph-capturable (the mask reads seq_lens in-graph).
     q: [B, H, D]; caches [B, Hkv, Smax, D]; returns [B, H, D]."""
-    import math
-
+    if not _on_gpu(q):
+        return torch_ref.decode_attention(q, k_cache, v_cache, seq_lens, scale)
     B, H, D = q.shape
     Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
     G = H // Hkv
-    s = scale if scale is not None else 1.0 / math.sqrt(D)
-    if not _on_gpu(q):
-        return torch_ref.decode_attention(q, k_cache, v_cache, seq_lens, scale)
+    s = _attn_scale(q, scale)
     mask = (torch.arange(Smax, device=q.device)[None, :]
             >= seq_lens[:, None]).view(B, 1, 1, Smax)
     qg = q.view(B * Hkv, G, D)

@@ -5,13 +5,15 @@
 //    (row-major D-stride tiles are an up-to-16-way bank conflict — guide §6
 //    G4), V staged transposed so the PV B-fragment is a contiguous
 //    ds_read_b128, P round-trips through padded LDS for the C→A relayout.
-//  * decode_attn — single-token decode: one block per (batch, head),
-//    chunked online softmax over the contiguous KV cache; score phase is
-//    thread-per-key, PV phase is thread-per-dim (coalesced V reads).
+//  * decode_attn — single-token decode, split-S ("flash-decoding"): one
+//    block per (kv-head, batch, split) streams its key range of the
+//    contiguous KV cache once for all G query heads of the group with a
+//    chunked online softmax; a combine kernel reduces the splits.
 //
 // Replaces (K6 prefill/decode in SURVEY §2.3) the reference's remote
 // /chat/completions calls (reference src/core/llm/providers/openai.py:117).
 #include "common.h"
+#include "sentio_kernels.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -313,266 +315,41 @@ __global__ void flash_attn_kernel(
 
 // ------------------------------------------------------------ decode attn
 // q [B, H, D], k/v cache [B, Hkv, Smax, D], seq_lens [B] -> out [B, H, D].
-// Block (256 threads) per (b, h).  Chunked online softmax:
-//   phase A: thread-per-key dot products (vectorized K row reads)
-//   phase B: thread-per-dim PV accumulation (coalesced V reads)
-#define DEC_CHUNK 256
-#define DEC_MAXG 8   // max query heads per kv head handled by one block
+#define DEC_CHUNK 256   // keys per online-softmax chunk == threads per block
+#define DEC_MAXG 8      // max query heads per kv head handled by one block
 
 // GQA-aware: one block per (batch, kv-head) streams the KV cache ONCE and
 // serves all G = H/Hkv query heads of the group — 1/G the HBM traffic of a
 // block-per-query-head layout.  Template on G so per-thread accumulator
 // arrays stay in registers (guide §5.4 rule 20).
-// Split-S ("flash-decoding") layout: grid (Hkv, B, SPLITS); each split
-// streams its contiguous key range once for all G heads and writes
-// UNNORMALIZED partials (o = sum exp(s-m) v, plus m and l) to the
-// workspace; a combine kernel reduces the splits.  SPLITS is chosen to
-// fill the 256 CUs (Hkv*B alone is 0.5 blocks/CU at common shapes).
+// Split-S ("flash-decoding") contract: grid (Hkv, B, SPLITS); each split
+// takes a contiguous 1/SPLITS of the VALID range [0, seq_lens[b]) (not of
+// Smax: splitting the allocation left the low splits with full spans and
+// the tail split nearly idle), streams it once for all G heads and writes
+// UNNORMALIZED partials to the workspace
+//   ws_o  [B, Hkv, SPLITS, G, D]   o = sum exp(s - m) v
+//   ws_ml [B, Hkv, SPLITS, G, 2]   running max m, sum l (m = -inf: empty)
+// which decode_attn_combine_kernel reduces.  SPLITS is chosen to fill the
+// 256 CUs (Hkv*B alone is 0.5 blocks/CU at common shapes).  At SPLITS == 1
+// (the 64-slot continuous-serving shape: B*Hkv already fills the chip) the
+// block normalizes and writes `out` itself — no combine launch, no fp32
+// workspace round-trip.
 // DT: compile-time head dim.  Every inner loop gets a compile-time trip
 // count so the compiler unrolls and BATCHES the global loads — the dynamic
 // version compiled to ONE load + s_waitcnt(0) per iteration (zero
 // memory-level parallelism; measured 87 us where streaming SoL is ~17 us).
-template <int G, int DT>
-__launch_bounds__(DEC_CHUNK, 1)   // LDS caps at 2 blocks/CU anyway: take the
-                                  // full VGPR budget, no scratch spills
-__global__ void decode_attn_split_kernel(
-    const bf16* __restrict__ q, const bf16* __restrict__ kc,
-    const bf16* __restrict__ vc,
-    float* __restrict__ ws_o,      // [B, Hkv, SPLITS, G, D]
-    float* __restrict__ ws_ml,     // [B, Hkv, SPLITS, G, 2]
-    bf16* __restrict__ out,        // [B, H, D] (written directly at splits==1)
-    const int* __restrict__ seq_lens,
-    int H, int Hkv, int Smax, int D_, float scale, int splits) {
-  constexpr int D = DT;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* p_sh = reinterpret_cast<float*>(smem);            // [G][DEC_CHUNK]
-  float* q_sh = p_sh + G * DEC_CHUNK;                      // [G][D]
-  float* red = q_sh + G * D;                               // [32] scratch
-  float* o_sh = red + 32;                                  // [G][D] final reduce
-  char* k_lds = reinterpret_cast<char*>(o_sh + G * D);     // [DEC_CHUNK][D] bf16 swizzled
-  // typed 16-byte-element view: keeps every staging/dot ds op a full
-  // ds_write_b128/ds_read_b128 — char* + XOR addressing hid the 16 B
-  // alignment from the compiler, which fragmented the dot phase into
-  // b96/b64/b32 pieces with serial lgkmcnt waits (seen in ISA)
-  bf16x8* k_vec = reinterpret_cast<bf16x8*>(k_lds);
-
-  const int hkv = blockIdx.x;
-  const int b = blockIdx.y;
-  const int split = blockIdx.z;
-  const int slen = seq_lens[b];
-  // split the VALID range (not Smax): splitting by the allocation left the
-  // low splits with full spans and the tail split nearly idle
-  const int span = (slen + splits - 1) / splits;
-  const int s_begin = split * span;
-  const int s_end = min(slen, s_begin + span);
-  const bf16* kb = kc + ((long)b * Hkv + hkv) * Smax * (long)D;
-  const bf16* vb = vc + ((long)b * Hkv + hkv) * Smax * (long)D;
-
-  for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
-    const int g = i / D, d = i % D;
-    q_sh[i] = bf2f(q[((long)b * H + hkv * G + g) * D + d]);
-    o_sh[i] = 0.f;
-  }
-  __syncthreads();
-
-  float m_run[G], l_run[G], alpha[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { m_run[g] = -INFINITY; l_run[g] = 0.f; }
-
-  // phase-B layout: all 256 threads active — thread owns 8 dims (dgroup) of
-  // every 16th key row (jslot).  16-byte V loads; 16 lanes cover a 256B row,
-  // a wave streams 4 rows, the block keeps 16 rows in flight.  Per-thread
-  // partial O accumulates across ALL chunks (rescaled by alpha like the
-  // softmax state) and is LDS-reduced once at the end.
-  const int dgroup = threadIdx.x & 15;       // owns dims dgroup*8 .. +7
-  const int jslot = threadIdx.x >> 4;        // keys j ≡ jslot (mod 16)
-  const int dgD = D / 8;                     // dgroups that exist (D=128 → 16)
-  const bool dg_ok = dgroup < dgD;
-  float o_part[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o_part[g][e] = 0.f;
-
-  const int Dbytes = D * 2;
-  for (int s0 = s_begin; s0 < s_end; s0 += DEC_CHUNK) {
-    const int chunk = min(DEC_CHUNK, s_end - s0);
-    // phase A1: cooperative coalesced K staging into XOR-swizzled LDS.
-    // One predicated unrolled path for EVERY chunk (a separate dynamic tail
-    // loop serialized one load per s_waitcnt and dominated short spans):
-    // 8 loads in flight before any ds_write; out-of-range rows stage zeros.
-    {
-      constexpr int IT = D / 8;          // loads per thread for a full chunk
-      constexpr int BATCH = 8;           // loads in flight
-      const int lim = chunk * D;
-#pragma unroll
-      for (int u0 = 0; u0 < IT; u0 += BATCH) {
-        bf16x8 tmp[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int i = threadIdx.x * 8 + (u0 + u) * DEC_CHUNK * 8;
-          if (i < lim) {
-            tmp[u] = nt_load8(
-                reinterpret_cast<const short*>(kb + (long)(s0 + i / D) * D)
-                + (i % D));
-          } else {
-            bf16x8 z = {};
-            tmp[u] = z;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int i = threadIdx.x * 8 + (u0 + u) * DEC_CHUNK * 8;
-          const int row = i / D, d = i % D;
-          k_vec[((row * Dbytes + d * 2) ^ ((row & 7) << 4)) >> 4] = tmp[u];
-        }
-      }
-    }
-    __syncthreads();
-    // phase A2: thread-per-key dot vs all G query heads, K read from LDS;
-    // scores stay in registers (the softmax below is the same thread).
-    float sc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) sc[g] = -INFINITY;
-    {
-      const int row = threadIdx.x;
-      if (row < chunk) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) sc[g] = 0.f;
-        for (int d = 0; d < D; d += 8) {
-          bf16x8 k8 = k_vec[((row * Dbytes + d * 2) ^ ((row & 7) << 4)) >> 4];
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-            float acc = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              acc += bits2f(k8[e]) * q_sh[g * D + d + e];
-            sc[g] += acc;
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) sc[g] *= scale;
-      }
-    }
-    // issue ALL of this thread's V loads for the chunk NOW — they do not
-    // depend on the softmax, so the HBM pipe stays busy while the block
-    // reductions run (otherwise it idles through both reduction barriers).
-    // (Measured dead ends kept out: half-depth V prefetch to save VGPRs
-    // lost 6% — LDS, not VGPRs, caps occupancy at 2 blocks/CU; a
-    // cross-chunk register-pipelined K prefetch lost 20% — the in-order
-    // vmcnt counter makes later V waits drain it, and the doubled VGPRs
-    // halved occupancy.)
-    constexpr int JT = DEC_CHUNK / 16;
-    bf16x8 v8[JT];
-    if (dg_ok) {
-#pragma unroll
-      for (int u = 0; u < JT; ++u) {
-        const int j = jslot + u * 16;
-        if (j < chunk) {
-          v8[u] = nt_load8(
-              reinterpret_cast<const short*>(vb + (long)(s0 + j) * D) +
-              dgroup * 8);
-        } else {
-          bf16x8 z = {};
-          v8[u] = z;
-        }
-      }
-    }
-    // batched per-head softmax: ONE reduction pair for all G maxima, one
-    // for all G sums (was 3 barriers × 2 reductions × G heads).
-    {
-      float mx[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) mx[g] = sc[g];
-      block_reduce_vec<G, true>(mx, red);
-      float sums[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float m_new = fmaxf(m_run[g], mx[g]);
-        float a = (m_run[g] == -INFINITY) ? 0.f : __expf(m_run[g] - m_new);
-        if (m_new == -INFINITY) a = 1.f;
-        alpha[g] = a;
-        const float p = (sc[g] != -INFINITY) ? __expf(sc[g] - m_new) : 0.f;
-        p_sh[g * DEC_CHUNK + threadIdx.x] = p;
-        sums[g] = p;
-        m_run[g] = m_new;
-      }
-      block_reduce_vec<G, false>(sums, red);  // barrier also publishes p_sh
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        l_run[g] = l_run[g] * alpha[g] + sums[g];
-    }
-    // phase B: PV consume — V already in flight since before the softmax.
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o_part[g][e] *= alpha[g];
-    if (dg_ok) {
-#pragma unroll
-      for (int u = 0; u < JT; ++u) {
-        const int j = jslot + u * 16;
-        if (j >= chunk) continue;       // p is 0 there anyway
-        float vf[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vf[e] = bits2f(v8[u][e]);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float p = p_sh[g * DEC_CHUNK + j];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o_part[g][e] += p * vf[e];
-        }
-      }
-    }
-    __syncthreads();
-  }
-
-  // reduce the 16 jslot partials per (g, dim) through LDS float atomics
-  if (dg_ok) {
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        atomicAdd(&o_sh[g * D + dgroup * 8 + e], o_part[g][e]);
-  }
-  __syncthreads();
-
-  if (splits == 1) {
-    // single split (the 64-slot continuous-serving shape: B*Hkv already
-    // fills the chip): normalize HERE and skip the combine kernel + the
-    // fp32 workspace round-trip entirely
-    for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
-      const int g = i / D, d = i % D;
-      const float den = l_run[g] > 0.f ? l_run[g] : 1.f;
-      out[((long)b * H + hkv * G + g) * D + d] = f2bf(o_sh[i] / den);
-    }
-    return;
-  }
-  // write unnormalized partials for this split
-  const long base = (((long)b * Hkv + hkv) * splits + split) * G;
-  for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
-    const int g = i / D, d = i % D;
-    ws_o[(base + g) * D + d] = o_sh[i];
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      ws_ml[(base + g) * 2 + 0] = m_run[g];
-      ws_ml[(base + g) * 2 + 1] = l_run[g];
-    }
-  }
-}
-
-// ---------------- cooperative-row decode kernel (occupancy variant) ----
-// Same split-S contract as decode_attn_split_kernel, but phase A loads K
-// rows COOPERATIVELY — a 16-lane group reads one 256 B row per iteration
-// (1 KB coalesced per wave-instruction) — and reduces the per-lane
-// partial dots with group16 shuffles instead of staging K through a
-// 64 KB LDS tile.  LDS drops to ~10 KB and (with half-depth V prefetch)
-// VGPRs to ~170, so residency can rise from 2 to 3 blocks/CU: the PMC
-// wave-state split showed the staged kernel 48% parked on waits/barriers
-// at 2 blocks/CU.  Each lane's q slice (8 dims x G heads) is
-// loop-invariant and lives in registers.  Select with
-// SENTIO_DECODE_COOP=1 (read once at first launch).
+// Phase A loads K rows COOPERATIVELY — a 16-lane group reads one 256 B row
+// per iteration (1 KB coalesced per wave-instruction), each lane dots its
+// 8-dim slice against its loop-invariant register copy of q (8 dims x G
+// heads), group16 shuffles reduce the partials.  Phase B: a thread owns 8
+// dims of every 16th key row (16 B V loads); its partial O accumulates
+// across ALL chunks, rescaled by alpha like the softmax state, and is
+// LDS-reduced once at the end.  ~10 KB LDS, ~170 VGPRs: 3 blocks/CU.
+// Measured dead ends, kept out: staging K through a 64 KB XOR-swizzled LDS
+// tile (2 blocks/CU, PMC wave-state split 48% parked on waits/barriers,
+// 8-13% slower across shapes); a cross-chunk register-pipelined K prefetch
+// (-20%: the in-order vmcnt counter makes later V waits drain it, and the
+// doubled VGPRs halved occupancy).
 template <int G, int DT>
 __launch_bounds__(DEC_CHUNK, 1)
 __global__ void decode_attn_coop_kernel(
@@ -811,23 +588,25 @@ __global__ void decode_attn_combine_kernel(
   }
 }
 
-extern "C" {
-
-hipError_t sentio_flash_attn(const void* q, const void* k, const void* v,
-                             void* out, const int* kv_lens, int B, int S,
-                             int H, int Hkv, int D, float scale, int causal,
-                             hipStream_t stream) {
+// One launcher for both prefill entry points: CACHE_SRC picks the K/V
+// layout, plain prefill passes Smax = q_off = 0.
+template <bool CACHE_SRC>
+static hipError_t launch_flash_attn(const void* q, const void* k,
+                                    const void* v, void* out,
+                                    const int* kv_lens, int B, int S, int H,
+                                    int Hkv, int D, float scale, int causal,
+                                    int Smax, int q_off, hipStream_t stream) {
   size_t lds = (size_t)KVBLK * D * 2 * 2   // K (swizzled) + V (tr image)
                + FA_WAVES * FA_QT * QBLK * P_STRIDE;
   const int wave_rows = FA_QT * QBLK;
   dim3 grid((S + FA_WAVES * wave_rows - 1) / (FA_WAVES * wave_rows), H, B);
 #define FA_CASE(DV)                                                          \
   case DV:                                                                   \
-    hipLaunchKernelGGL((flash_attn_kernel<DV, false>), grid,               \
-                       dim3(FA_WAVES * WAVE), lds,                            \
+    hipLaunchKernelGGL((flash_attn_kernel<DV, CACHE_SRC>), grid,             \
+                       dim3(FA_WAVES * WAVE), lds,                           \
                        stream, (const bf16*)q, (const bf16*)k,               \
                        (const bf16*)v, (bf16*)out, kv_lens, B, S, H, Hkv, D, \
-                       scale, causal, 0, 0);                                 \
+                       scale, causal, Smax, q_off);                          \
     break;
   switch (D) {
     FA_CASE(32) FA_CASE(64) FA_CASE(96) FA_CASE(128)
@@ -839,31 +618,23 @@ hipError_t sentio_flash_attn(const void* q, const void* k, const void* v,
   return hipSuccess;
 }
 
+extern "C" {
+
+hipError_t sentio_flash_attn(const void* q, const void* k, const void* v,
+                             void* out, const int* kv_lens, int B, int S,
+                             int H, int Hkv, int D, float scale, int causal,
+                             hipStream_t stream) {
+  return launch_flash_attn<false>(q, k, v, out, kv_lens, B, S, H, Hkv, D,
+                                  scale, causal, 0, 0, stream);
+}
+
 hipError_t sentio_flash_attn_cache(const void* q, const void* kc,
                                    const void* vc, void* out,
                                    const int* kv_lens, int B, int S, int H,
                                    int Hkv, int Smax, int D, float scale,
                                    int q_off, hipStream_t stream) {
-  size_t lds = (size_t)KVBLK * D * 2 * 2
-               + FA_WAVES * FA_QT * QBLK * P_STRIDE;
-  const int wave_rows = FA_QT * QBLK;
-  dim3 grid((S + FA_WAVES * wave_rows - 1) / (FA_WAVES * wave_rows), H, B);
-#define FAC_CASE(DV)                                                         \
-  case DV:                                                                   \
-    hipLaunchKernelGGL((flash_attn_kernel<DV, true>), grid,                \
-                       dim3(FA_WAVES * WAVE), lds,                            \
-                       stream, (const bf16*)q, (const bf16*)kc,              \
-                       (const bf16*)vc, (bf16*)out, kv_lens, B, S, H, Hkv,   \
-                       D, scale, 1, Smax, q_off);                            \
-    break;
-  switch (D) {
-    FAC_CASE(32) FAC_CASE(64) FAC_CASE(96) FAC_CASE(128)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef FAC_CASE
-  HIP_CHECK_LAUNCH();
-  return hipSuccess;
+  return launch_flash_attn<true>(q, kc, vc, out, kv_lens, B, S, H, Hkv, D,
+                                 scale, 1, Smax, q_off, stream);
 }
 
 hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
@@ -871,50 +642,31 @@ hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
                               float* ws_o, float* ws_ml, int splits,
                               int B, int H, int Hkv, int Smax, int D,
                               float scale, hipStream_t stream) {
-  if (D > 256 || (D % 8)) return hipErrorInvalidValue;
   const int G = H / Hkv;
-  if (G > DEC_MAXG || H % Hkv) return hipErrorInvalidValue;
-  size_t lds = (size_t)(G * DEC_CHUNK + 2 * G * D + 32) * sizeof(float)
-               + (size_t)DEC_CHUNK * D * 2;   // swizzled K stage
+  if (H % Hkv || G > DEC_MAXG || (D != 64 && D != 128))
+    return hipErrorInvalidValue;
+  // p_sh [G][DEC_CHUNK] | q_sh [G][D] | red [32] | o_sh [G][D]
+  const size_t lds = (size_t)(G * DEC_CHUNK + 2 * G * D + 32) * sizeof(float);
   dim3 grid(Hkv, B, splits);
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  static int use_coop = -1;
-  if (use_coop < 0) {
-    // cooperative-row kernel is the default (measured +8-13% over the
-    // LDS-staged kernel across splits/batch shapes); =0 opts out
-    const char* e = std::getenv("SENTIO_DECODE_COOP");
-    use_coop = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (use_coop)
-    lds = (size_t)(G * DEC_CHUNK + 2 * G * D + 32) * sizeof(float);
 #define DEC_CASE(GV, DV)                                                      \
-  if (use_coop) {                                                             \
+  case GV * 1000 + DV:                                                        \
     hipLaunchKernelGGL((decode_attn_coop_kernel<GV, DV>), grid,               \
                        dim3(DEC_CHUNK), lds, stream, (const bf16*)q,          \
                        (const bf16*)kc, (const bf16*)vc, ws_o, ws_ml,         \
                        (bf16*)out, seq_lens, H, Hkv, Smax, D, scale, splits); \
-  } else {                                                                    \
-    hipLaunchKernelGGL((decode_attn_split_kernel<GV, DV>), grid,              \
-                       dim3(DEC_CHUNK), lds, stream, (const bf16*)q,          \
-                       (const bf16*)kc, (const bf16*)vc, ws_o, ws_ml,         \
-                       (bf16*)out, seq_lens, H, Hkv, Smax, D, scale, splits); \
-  }                                                                           \
-  break;
+    break;
+#define DEC_ALL_G(DV)                                                 \
+  DEC_CASE(1, DV) DEC_CASE(2, DV) DEC_CASE(3, DV) DEC_CASE(4, DV)     \
+  DEC_CASE(5, DV) DEC_CASE(6, DV) DEC_CASE(7, DV) DEC_CASE(8, DV)
   switch (G * 1000 + D) {
-    case 1064: DEC_CASE(1, 64) case 2064: DEC_CASE(2, 64)
-    case 3064: DEC_CASE(3, 64) case 4064: DEC_CASE(4, 64)
-    case 5064: DEC_CASE(5, 64) case 6064: DEC_CASE(6, 64)
-    case 7064: DEC_CASE(7, 64) case 8064: DEC_CASE(8, 64)
-    case 1128: DEC_CASE(1, 128) case 2128: DEC_CASE(2, 128)
-    case 3128: DEC_CASE(3, 128) case 4128: DEC_CASE(4, 128)
-    case 5128: DEC_CASE(5, 128) case 6128: DEC_CASE(6, 128)
-    case 7128: DEC_CASE(7, 128) case 8128: DEC_CASE(8, 128)
-    default:
+    DEC_ALL_G(64) DEC_ALL_G(128)
+    default:   // G < 1
       return hipErrorInvalidValue;
   }
+#undef DEC_ALL_G
 #undef DEC_CASE
   HIP_CHECK_LAUNCH();
-  if (splits > 1) {   // splits==1 normalized + wrote out in the split kernel
+  if (splits > 1) {   // splits==1 normalized + wrote out in the decode kernel
     hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(H, B), dim3(128), 0,
                        stream, ws_o, ws_ml, (bf16*)out, H, G, D, splits);
     HIP_CHECK_LAUNCH();
@@ -923,3 +675,4 @@ hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
 }
 
 }  // extern "C"
+

@@ -1,60 +1,14 @@
 // Torch bindings for the sentio gfx950 kernels.  The only TU that includes
-// torch headers (slow compile); kernels live in sibling .hip TUs exposed
-// through the C API in sentio_kernels.h.
+// torch headers (slow compile); the kernels live in the sibling .hip TUs and
+// are called through the C API declared in sentio_kernels.h, which those
+// TUs include too, so the compiler checks every call here against the
+// definitions.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
-extern "C" {
-hipError_t sentio_rmsnorm(const void*, const void*, void*, long, int, float,
-                          hipStream_t);
-hipError_t sentio_rmsnorm_residual(const void*, const void*, const void*,
-                                   void*, void*, long, int, float, hipStream_t);
-hipError_t sentio_swiglu(const void*, const void*, void*, long, hipStream_t);
-hipError_t sentio_swiglu_packed(const void*, void*, long, int, hipStream_t);
-hipError_t sentio_rope(const void*, void*, const float*, const float*,
-                       const int*, int, int, int, int, hipStream_t);
-hipError_t sentio_softmax(const void*, void*, long, int, hipStream_t);
-hipError_t sentio_decode_qkv_prep(const void*, void*, void*, void*,
-                                  const float*, const float*, const int*, int,
-                                  int, int, int, int, hipStream_t);
-hipError_t sentio_mean_pool_l2norm(const void*, const unsigned char*, float*,
-                                   int, int, int, hipStream_t);
-hipError_t sentio_sample(const float*, long*, float*, int*, int, int, float,
-                         unsigned, hipStream_t);
-hipError_t sentio_sample_support(const float*, const float*, const int*,
-                                 const float*, float*, int*, long, int,
-                                 hipStream_t);
-hipError_t sentio_sample_filtered(const float*, const float*, const int*,
-                                  const float*, const long*, const int*, long*,
-                                  long, int, hipStream_t);
-hipError_t sentio_cosine_scores_f16(const void*, const void*, float*, long,
-                                    int, int, hipStream_t);
-hipError_t sentio_cosine_scores_bf16(const void*, const void*, float*, long,
-                                     int, int, hipStream_t);
-hipError_t sentio_bm25(const long*, const long*, const long*, const int*,
-                       const float*, const float*, const float*, float*, int,
-                       long, float, float, float, float, hipStream_t);
-hipError_t sentio_flash_attn(const void*, const void*, const void*, void*,
-                             const int*, int, int, int, int, int, float, int,
-                             hipStream_t);
-hipError_t sentio_decode_attn(const void*, const void*, const void*, void*,
-                              const int*, float*, float*, int, int, int, int,
-                              int, int, float, hipStream_t);
-hipError_t sentio_flash_attn_cache(const void*, const void*, const void*,
-                                   void*, const int*, int, int, int, int,
-                                   int, int, float, int, hipStream_t);
-hipError_t sentio_gemm_bf16(const void*, const void*, void*, int, int, int,
-                            hipStream_t);
-hipError_t sentio_skinny_gemm(const void*, const void*, void*, int, int, int,
-                              hipStream_t);
-int sentio_lt_gemm_tn(const void*, const void*, void*, int, int, int,
-                      hipStream_t);
-hipError_t sentio_fuse_topk(const long*, const float*, const long*,
-                            const float*, long*, float*, int, int, int, int,
-                            int, float, float, float, hipStream_t);
-}
+#include "sentio_kernels.h"
 
 namespace {
 
@@ -322,7 +276,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   splits = std::max(1, std::min(splits, max_splits));
   if (const char* ov = std::getenv("SENTIO_DECODE_SPLITS"))
     splits = std::max(1, std::min(atoi(ov), max_splits));
-  // splits==1 writes `out` directly from the split kernel (no combine):
+  // splits==1 writes `out` directly from the decode kernel (no combine):
   // keep only dummy workspaces
   const long ws_n = splits > 1 ? (long)B * Hkv * splits * G : 1;
   auto ws_o = torch::empty({ws_n * D}, q.options().dtype(torch::kFloat));

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <hipblaslt/hipblaslt.h>
 
+#include "sentio_kernels.h"
+
 #include <cstdio>
 #include <map>
 #include <mutex>

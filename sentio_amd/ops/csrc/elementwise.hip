@@ -3,6 +3,7 @@
 // All bf16 I/O with fp32 accumulation; vectorized bf16x8 loads per
 // cdna_hip_programming.md G13 (scalar bf16 loads are ~2x slower).
 #include "common.h"
+#include "sentio_kernels.h"
 
 // ---------------------------------------------------------------- rmsnorm
 // x [N, D] bf16, w [D] bf16 -> y [N, D] bf16.  One block per row.

@@ -7,6 +7,7 @@
 // plain library-shaped projections go through hipBLASLt (torch.matmul).
 // C = A[M,K] @ B[K,N], all row-major bf16, fp32 accumulate.
 #include "common.h"
+#include "sentio_kernels.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -261,10 +262,6 @@ hipError_t sentio_skinny_gemm(const void* x, const void* w, void* out, int M,
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }
-
-}  // extern "C"
-
-extern "C" {
 
 hipError_t sentio_gemm_bf16(const void* A, const void* B, void* C, int M,
                             int N, int K, hipStream_t stream) {

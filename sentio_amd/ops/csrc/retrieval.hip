@@ -3,6 +3,7 @@
 // the cosine scan reads each index row exactly once and amortizes it over
 // all B queries of the batch (queries staged in LDS).
 #include "common.h"
+#include "sentio_kernels.h"
 
 // mat [N, D] f16-or-bf16 row-major (L2-normalized rows), q [B, D] same dtype
 // (normalized), scores [B, N] f32.

@@ -26,6 +26,7 @@
 // consecutive bins in registers, so the hot bin takes one LDS atomic per
 // thread and pass instead of one per token.
 #include "common.h"
+#include "sentio_kernels.h"
 
 typedef unsigned long long u64;
 

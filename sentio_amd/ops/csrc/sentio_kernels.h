@@ -1,0 +1,102 @@
+// C API of the sentio gfx950 kernels: every extern "C" entry point, declared
+// once.  Each kernel TU includes this next to its definitions and
+// bindings.hip includes it for its calls; extern "C" functions cannot be
+// overloaded, so a definition or call that disagrees with a declaration
+// here is a compile error instead of a silently mis-linked symbol.
+// All pointers are device pointers; launches go to `stream`.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// ---- elementwise.hip
+hipError_t sentio_rmsnorm(const void* x, const void* w, void* y, long rows,
+                          int D, float eps, hipStream_t stream);
+hipError_t sentio_rmsnorm_residual(const void* x, const void* res,
+                                   const void* w, void* y, void* h, long rows,
+                                   int D, float eps, hipStream_t stream);
+hipError_t sentio_swiglu(const void* gate, const void* up, void* out, long n,
+                         hipStream_t stream);
+// F is the OUTPUT width (half the packed [gate | up] row)
+hipError_t sentio_swiglu_packed(const void* gu, void* out, long rows, int F,
+                                hipStream_t stream);
+hipError_t sentio_rope(const void* x, void* y, const float* cosT,
+                       const float* sinT, const int* pos, int B, int S, int H,
+                       int D, hipStream_t stream);
+// trailing dims are (D, Smax) here but (Smax, D) in the attention entry points
+hipError_t sentio_decode_qkv_prep(const void* qkv, void* q_out, void* kc,
+                                  void* vc, const float* cosT,
+                                  const float* sinT, const int* seq_lens,
+                                  int B, int H, int Hkv, int D, int Smax,
+                                  hipStream_t stream);
+hipError_t sentio_softmax(const void* x, void* y, long rows, int D,
+                          hipStream_t stream);
+hipError_t sentio_mean_pool_l2norm(const void* hidden,
+                                   const unsigned char* mask, float* out,
+                                   int B, int S, int D, hipStream_t stream);
+hipError_t sentio_sample(const float* logits, long* out, float* ws_val,
+                         int* ws_idx, int B, int V, float temperature,
+                         unsigned seed, hipStream_t stream);
+
+// ---- sampling.hip
+hipError_t sentio_sample_support(const float* logits, const float* temperature,
+                                 const int* top_k, const float* top_p,
+                                 float* tau, int* count, long B, int V,
+                                 hipStream_t stream);
+hipError_t sentio_sample_filtered(const float* logits, const float* temperature,
+                                  const int* top_k, const float* top_p,
+                                  const long* seed, const int* step, long* out,
+                                  long B, int V, hipStream_t stream);
+
+// ---- retrieval.hip
+// index matrix first, queries second; dims are (N, D, B)
+hipError_t sentio_cosine_scores_f16(const void* mat, const void* q,
+                                    float* scores, long N, int D, int B,
+                                    hipStream_t stream);
+hipError_t sentio_cosine_scores_bf16(const void* mat, const void* q,
+                                     float* scores, long N, int D, int B,
+                                     hipStream_t stream);
+hipError_t sentio_bm25(const long* term_ids, const long* qoff,
+                       const long* starts, const int* post_doc,
+                       const float* post_tf, const float* idf,
+                       const float* doc_len, float* scores, int T, long total,
+                       float k1, float b, float avgdl, float delta,
+                       hipStream_t stream);
+hipError_t sentio_fuse_topk(const long* d_ids, const float* d_scores,
+                            const long* s_ids, const float* s_scores,
+                            long* out_ids, float* out_scores, int B, int Kd,
+                            int Ks, int top_k, int method, float rrf_k,
+                            float dw, float sw, hipStream_t stream);
+
+// ---- attention.hip
+hipError_t sentio_flash_attn(const void* q, const void* k, const void* v,
+                             void* out, const int* kv_lens, int B, int S,
+                             int H, int Hkv, int D, float scale, int causal,
+                             hipStream_t stream);
+// Smax sits BEFORE D here; always causal, q_off replaces the causal flag
+hipError_t sentio_flash_attn_cache(const void* q, const void* kc,
+                                   const void* vc, void* out,
+                                   const int* kv_lens, int B, int S, int H,
+                                   int Hkv, int Smax, int D, float scale,
+                                   int q_off, hipStream_t stream);
+// splits comes BEFORE the shape; no S (one query token per row)
+hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
+                              void* out, const int* seq_lens, float* ws_o,
+                              float* ws_ml, int splits, int B, int H, int Hkv,
+                              int Smax, int D, float scale,
+                              hipStream_t stream);
+
+// ---- gemm.hip / blaslt.hip
+// B is [K, N] row-major; dims are (M, N, K)
+hipError_t sentio_gemm_bf16(const void* A, const void* B, void* C, int M,
+                            int N, int K, hipStream_t stream);
+// w is [N, K] row-major (TN); dims are (M, K, N) — NOT (M, N, K)
+hipError_t sentio_skinny_gemm(const void* x, const void* w, void* out, int M,
+                              int K, int N, hipStream_t stream);
+// w is [N, K] row-major (TN) like skinny_gemm, but dims are (M, N, K);
+// returns 0 on success, not a hipError_t
+int sentio_lt_gemm_tn(const void* x, const void* w, void* out, int M, int N,
+                      int K, hipStream_t stream);
+
+}  // extern "C"

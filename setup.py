@@ -43,18 +43,17 @@ def build(verbose: bool = True) -> Path:
     # SENTIO_SANITIZE=1: host-side ASan+UBSan test build (SURVEY §5 race/
     # sanitizer row).  Run with LD_PRELOAD of the ASan runtime, e.g.
     #   LD_PRELOAD=$(hipcc -print-file-name=libclang_rt.asan-x86_64.so) pytest
-    if os.environ.get("SENTIO_DECODE_GLDS") == "1":
-        # experimental LDS-DMA K staging in decode attention
-        common += ["-DSENTIO_DECODE_GLDS"]
     if os.environ.get("SENTIO_SANITIZE") == "1":
         common += ["-fsanitize=address,undefined",
                    "-fno-omit-frame-pointer", "-shared-libasan"]
     objs = []
+    # every TU includes the csrc headers: editing any of them rebuilds all
+    headers_mtime = max(h.stat().st_mtime for h in CSRC.glob("*.h"))
 
     def compile_tu(src: Path, extra: list[str]) -> Path:
         obj = build_dir / (src.stem + ".o")
         if obj.exists() and obj.stat().st_mtime > max(
-            src.stat().st_mtime, (CSRC / "common.h").stat().st_mtime
+            src.stat().st_mtime, headers_mtime
         ):
             return obj
         cmd = common + extra + ["-c", str(src), "-o", str(obj)]

@@ -118,6 +118,41 @@ def test_prefix_suffix_prefill_matches_full():
     assert torch.allclose(d1, d2, rtol=1e-4, atol=1e-4)
 
 
+def test_decode_attn_impl_fixed_at_construction(monkeypatch):
+    """The decode-attention function is resolved once in __init__ from
+    SENTIO_DECODE_ATTN and no prefill reassigns it."""
+    from sentio_amd import ops
+    from sentio_amd.engines.configs import MODEL_CONFIGS
+    from sentio_amd.engines.transformer import KVCache, Transformer
+
+    cfg = MODEL_CONFIGS["tiny-decoder"]
+    monkeypatch.delenv("SENTIO_DECODE_ATTN", raising=False)
+    m_default = Transformer(cfg, device="cpu", seed=5)
+    assert m_default.decode_attn is ops.decode_attention
+    for mode in ("auto", "hand"):
+        monkeypatch.setenv("SENTIO_DECODE_ATTN", mode)
+        assert Transformer(cfg, device="cpu", seed=5).decode_attn \
+            is ops.decode_attention
+    monkeypatch.setenv("SENTIO_DECODE_ATTN", "bmm")
+    m_bmm = Transformer(cfg, device="cpu", seed=5)
+    assert m_bmm.decode_attn is ops.decode_attention_bmm
+    # the environment is not consulted again after construction
+    monkeypatch.delenv("SENTIO_DECODE_ATTN")
+
+    P, S = 6, 5
+    torch.manual_seed(4)
+    toks = torch.randint(0, cfg.vocab_size, (2, P + S))
+    for m, fn in ((m_default, ops.decode_attention),
+                  (m_bmm, ops.decode_attention_bmm)):
+        cache = KVCache(cfg, 2, 32, "cpu", m.dtype)
+        m.prefill(toks[:, :P], cache)
+        assert m.decode_attn is fn
+        m.prefill_suffix(toks[:, P:], cache, P)
+        assert m.decode_attn is fn
+        m.decode_step(toks[:, :1], cache)
+        assert m.decode_attn is fn
+
+
 def test_generate_with_prefix_kv_matches_disabled(monkeypatch):
     """Full generate() path: identical greedy tokens with prefix caching on
     and off (CPU fp32 — exact)."""

@@ -506,6 +506,32 @@ def test_decode_attn_gqa7(dev):
     _cmp(got, want, rtol=3e-2, atol=3e-2)
 
 
+@pytest.mark.parametrize("splits_env", [None, "1", "2"])
+@pytest.mark.parametrize("H,D", [(8, 128), (8, 64)])
+def test_decode_attn_split_combine(dev, monkeypatch, H, D, splits_env):
+    """Split-S decode + combine kernel at a serving-like Smax.  Unset gives
+    splits=3 here (ceil(512/8)=64 clamped to 768/256); "1" skips the
+    combine; "2" forces ragged spans.  lens cover a span of exactly one
+    256-key chunk (768/3), a ragged span (700), spans shorter than a chunk
+    (257) and completely empty splits (1), which the combine must ignore."""
+    from sentio_amd import ops
+
+    if splits_env is None:
+        monkeypatch.delenv("SENTIO_DECODE_SPLITS", raising=False)
+    else:
+        monkeypatch.setenv("SENTIO_DECODE_SPLITS", splits_env)
+    B, Hkv, Smax = 4, 2, 768
+    torch.manual_seed(13)
+    q = torch.randn(B, H, D, dtype=torch.bfloat16, device=dev)
+    kc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
+    vc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
+    lens = torch.tensor([768, 700, 257, 1], dtype=torch.int32, device=dev)
+    got = ops.decode_attention(q, kc, vc, lens)
+    want = ops.torch_ref.decode_attention(q.cpu().float(), kc.cpu().float(),
+                                          vc.cpu().float(), lens.cpu())
+    _cmp(got, want, rtol=3e-2, atol=3e-2)
+
+
 def test_attention_cache_matches_ref(dev):
     from sentio_amd import ops
 
