@@ -1,41 +1,73 @@
 """Isolated decode-attention microbenchmark (llama3-8b decode shape).
-Prints achieved µs + effective KV TB/s per splits setting.
-Run: gpurun -- 'python scripts/decode_attn_probe.py'"""
+Prints achieved µs + effective KV TB/s per (splits, waves) setting for
+ops.decode_attention, for the two-op chain decode_qkv_prep + decode_attention
+and for the one-launch ops.decode_attention_fused.
+Run: python scripts/decode_attn_probe.py [--repeats N] [--main-only]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sentio_amd import ops
 
-def bench(q, kc, vc, lens, iters=200):
+def bench(fn, iters=200):
     for _ in range(20):
-        ops.decode_attention(q, kc, vc, lens)
+        fn()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(iters):
-        ops.decode_attention(q, kc, vc, lens)
+        fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters
 
-def main():
+def setenv(name, val):
+    if val: os.environ[name] = str(val)
+    else: os.environ.pop(name, None)
+
+def main(repeats=1):
     if not torch.cuda.is_available():
         print(f"{__file__}: needs a GPU (MI355X) — skipping")
         return
 
     dev = "cuda:0"
+    has_fused = hasattr(ops, "decode_attention_fused")
     for B, slen in [(16, 1600), (32, 1600), (32, 512)]:
         H, Hkv, Smax, D = 32, 8, 2120, 128
         torch.manual_seed(0)
         q = torch.randn(B, H, D, dtype=torch.bfloat16, device=dev)
+        qkv = torch.randn(B, (H + 2 * Hkv) * D, dtype=torch.bfloat16,
+                          device=dev)
         kc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
         vc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
+        cos, sin = ops.torch_ref.rope_tables(Smax, D, device=dev)
         lens = torch.full((B,), slen, dtype=torch.int32, device=dev)
+        pos = lens - 1            # new token at slen-1: slen keys attended
         kv_bytes = 2 * B * Hkv * slen * D * 2
         print(f"--- B={B} slen={slen} (KV {kv_bytes/1e6:.0f} MB)")
-        for splits in (0, 1, 2, 4, 8):
-            if splits: os.environ["SENTIO_DECODE_SPLITS"] = str(splits)
-            else: os.environ.pop("SENTIO_DECODE_SPLITS", None)
-            t = bench(q, kc, vc, lens)
-            print(f"splits={splits or 'auto'}: {t*1e6:7.1f}us  {kv_bytes/t/1e12:.2f} TB/s")
+
+        def attn():
+            ops.decode_attention(q, kc, vc, lens)
+
+        def two_op():
+            ops.decode_attention(
+                ops.decode_qkv_prep(qkv, kc, vc, cos, sin, pos), kc, vc, lens)
+
+        def fused():
+            ops.decode_attention_fused(qkv, kc, vc, cos, sin, pos)
+
+        paths = [("attn", attn), ("prep+attn", two_op)]
+        if has_fused:
+            paths.append(("fused", fused))
+        for waves in (0, 4, 8) if has_fused else (0,):
+            setenv("SENTIO_DECODE_WAVES", waves)
+            for splits in (0, 1, 2, 4, 8):
+                setenv("SENTIO_DECODE_SPLITS", splits)
+                for name, fn in paths:
+                    ts = [bench(fn) for _ in range(repeats)]
+                    print(f"waves={waves or 'auto'} splits={splits or 'auto'} "
+                          f"{name:9s}: "
+                          + " ".join(f"{t*1e6:7.1f}" for t in ts)
+                          + f" us  {kv_bytes/min(ts)/1e12:.2f} TB/s")
+        setenv("SENTIO_DECODE_WAVES", 0)
+        setenv("SENTIO_DECODE_SPLITS", 0)
 
 
 
@@ -101,6 +133,9 @@ def flash_probe():
 
 
 if __name__ == "__main__":
-    main()
-    bmm_probe()
-    flash_probe()
+    reps = int(sys.argv[sys.argv.index("--repeats") + 1]) \
+        if "--repeats" in sys.argv else 1
+    main(reps)
+    if "--main-only" not in sys.argv:
+        bmm_probe()
+        flash_probe()

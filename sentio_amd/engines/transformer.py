@@ -260,30 +260,47 @@ class Transformer:
         return normed
 
     # ----- decode fast path: fused RoPE + KV-cache write + fused norms -----
+    def _decode_fused(self, x: torch.Tensor) -> bool:
+        """RoPE + KV write + attention in one launch: the hand kernel on the
+        GPU.  The bmm variant and the CPU keep the two-op path."""
+        return self.decode_attn is ops.decode_attention and x.is_cuda
+
     def _attn_decode(self, normed: torch.Tensor, layer: dict, cache: KVCache,
-                     layer_idx: int, attn_lens: torch.Tensor) -> torch.Tensor:
+                     layer_idx: int,
+                     attn_lens: torch.Tensor | None) -> torch.Tensor:
         B = normed.shape[0]
         d = self.cfg.dim
         hd = self.cfg.head_dim
         qkv = ops.lt_linear(normed.view(B, d), layer["wqkv"])
-        q = ops.decode_qkv_prep(qkv, cache.k[layer_idx], cache.v[layer_idx],
-                                self.rope_cos, self.rope_sin, cache.seq_lens)
-        out = self.decode_attn(q, cache.k[layer_idx], cache.v[layer_idx],
-                               attn_lens, self.scale)
+        if self._decode_fused(qkv):
+            # one launch: RoPE(q) in registers, KV row written and attended
+            out = ops.decode_attention_fused(
+                qkv, cache.k[layer_idx], cache.v[layer_idx], self.rope_cos,
+                self.rope_sin, cache.seq_lens, self.scale)
+        else:
+            q = ops.decode_qkv_prep(qkv, cache.k[layer_idx],
+                                    cache.v[layer_idx], self.rope_cos,
+                                    self.rope_sin, cache.seq_lens)
+            out = self.decode_attn(q, cache.k[layer_idx], cache.v[layer_idx],
+                                   attn_lens, self.scale)
         out = linear_row_parallel(out.view(B, self.h_local * hd),
                                   layer["wo"], self.tp, linear=ops.lt_linear)
         return out.view(B, 1, d)
 
     def forward_decode(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
-        """One-token decode: tokens [B, 1] → hidden [B, 1, dim].  Uses the
-        fused decode_qkv_prep kernel (RoPE + cache write in one launch) and
-        advances cache.seq_lens on device (hipGraph-capturable)."""
+        """One-token decode: tokens [B, 1] → hidden [B, 1, dim].  RoPE and
+        the cache write ride in the decode-attention launch
+        (ops.decode_attention_fused; decode_qkv_prep + attention on the bmm
+        and CPU paths).  decode_step advances cache.seq_lens on device
+        (hipGraph-capturable)."""
         B = tokens.shape[0]
         x = self.w.tok_emb[tokens.reshape(-1)].view(B, 1, self.cfg.dim)
         eps = self.cfg.norm_eps
         layers = self.w.layers
         n = len(layers)
-        attn_lens = cache.seq_lens + 1
+        # the fused op takes the new token's position; only the two-op
+        # path needs the key count
+        attn_lens = (None if self._decode_fused(x) else cache.seq_lens + 1)
         normed = ops.rmsnorm(x, layers[0]["attn_norm"], eps)
         for i, layer in enumerate(layers):
             a = self._attn_decode(normed, layer, cache, i, attn_lens)

@@ -150,6 +150,34 @@ def decode_attention(q, k_cache, v_cache, seq_lens, scale: float | None = None):
     return torch_ref.decode_attention(q, k_cache, v_cache, seq_lens, scale)
 
 
+def decode_attention_fused(qkv, k_cache, v_cache, cos, sin, seq_lens,
+                           scale: float | None = None):
+    """decode_qkv_prep + decode_attention in one kernel launch.
+    qkv: [B, (H+2*Hkv)*D] raw projection; seq_lens: [B] contiguous i32, the
+    position of the new token.  RoPE(q) never leaves registers, the new k/v
+    row is written to the caches at row seq_lens[b], and attention covers
+    seq_lens[b] + 1 keys.  Returns [B, H, D]."""
+    if qkv.dim() != 2 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("qkv must be [B, (H+2*Hkv)*D], caches [B,Hkv,Smax,D]")
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    if D not in (64, 128):
+        raise ValueError(f"head dim must be 64 or 128, got {D}")
+    H = qkv.shape[1] // D - 2 * Hkv
+    if H <= 0 or H % Hkv or (H + 2 * Hkv) * D != qkv.shape[1]:
+        raise ValueError(
+            f"qkv width {qkv.shape[1]} is not (H+2*{Hkv})*{D} for a whole "
+            "number of query heads per kv head")
+    if seq_lens.dtype != torch.int32 or not seq_lens.is_contiguous() \
+            or seq_lens.numel() != qkv.shape[0]:
+        raise ValueError("seq_lens must be a contiguous int32 [B] tensor")
+    s = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    if _on_gpu(qkv):
+        return _require_hip().decode_attn_fused(
+            qkv.contiguous(), k_cache, v_cache, cos, sin, seq_lens, s)
+    return torch_ref.decode_attention_fused(qkv, k_cache, v_cache, cos, sin,
+                                            seq_lens, s)
+
+
 def decode_attention_bmm(q, k_cache, v_cache, seq_lens,
                          scale: float | None = None):
     """Decode attention as two rocBLAS batched GEMMs over the FULL cache
@@ -357,7 +385,7 @@ def gemm_bf16(a, b):
 
 
 __all__ = [
-    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "swiglu", "swiglu_packed", "softmax",
+    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -8,7 +8,9 @@
 //  * decode_attn — single-token decode, split-S ("flash-decoding"): one
 //    block per (kv-head, batch, split) streams its key range of the
 //    contiguous KV cache once for all G query heads of the group with a
-//    chunked online softmax; a combine kernel reduces the splits.
+//    wave-private online softmax (no LDS or barrier in the key loop); a
+//    combine kernel reduces the splits when there is more than one.  The
+//    fused variant also applies RoPE and appends the new token's k/v row.
 //
 // Replaces (K6 prefill/decode in SURVEY §2.3) the reference's remote
 // /chat/completions calls (reference src/core/llm/providers/openai.py:117).
@@ -315,244 +317,338 @@ __global__ void flash_attn_kernel(
 
 // ------------------------------------------------------------ decode attn
 // q [B, H, D], k/v cache [B, Hkv, Smax, D], seq_lens [B] -> out [B, H, D].
-#define DEC_CHUNK 256   // keys per online-softmax chunk == threads per block
 #define DEC_MAXG 8      // max query heads per kv head handled by one block
 
-// GQA-aware: one block per (batch, kv-head) streams the KV cache ONCE and
-// serves all G = H/Hkv query heads of the group — 1/G the HBM traffic of a
-// block-per-query-head layout.  Template on G so per-thread accumulator
-// arrays stay in registers (guide §5.4 rule 20).
+// GQA-aware: one block per (batch, kv-head, split) streams its key span of
+// the KV cache ONCE and serves all G = H/Hkv query heads of the group — 1/G
+// the HBM traffic of a block-per-query-head layout.  Template on G, D and
+// the block width NW (waves) so every per-thread array stays in registers
+// and every inner loop has a compile-time trip count (a dynamic one
+// compiled to ONE load + s_waitcnt(0) per iteration: 87 us where streaming
+// SoL is ~17 us).
+//
+// Wave-private online softmax — no LDS and no barrier in the key loop.
+// In a wave, lane li = lane & 15 owns dims [li*8, li*8+8) and the 16-lane
+// group g4 = lane >> 4 owns one key per load instruction: four consecutive
+// cache rows per wave-instruction, 1 KB coalesced at D=128.  A lane loads
+// 16 B of K and 16 B of V of the SAME key, dots its K slice against its
+// register copy of q (pre-multiplied by scale*log2 e), a DPP butterfly
+// leaves the score in all 16 lanes of the group, and the group keeps its
+// OWN running max m[G], sum l[G] and its dim slice of O, o[G][8], updated
+// from its own keys only.  The max update and the rescale run once per
+// batch of KB keys per group; the batch's 2*KB loads issue back to back
+// before the first use, K first, so the waits are counted and V is still
+// in flight while the scores are formed.  Waves take batches of the block's
+// span interleaved (wave w: batches w, w+NW, ...), so a ragged span keeps
+// every wave busy to its end.  Loads clamp to the span (no exec-mask
+// predication: it forces conservative vmcnt(0) waits); clamped keys are
+// masked to -inf.  Once per block the four groups of a wave fold through
+// __shfl_xor 16/32 and the waves through NW*(G*D + 2G) floats of LDS with
+// a single barrier; every fold treats m = -inf (a group, wave or split
+// that owned no key) as weight 0, and l = 0 writes zeros.
+//
 // Split-S ("flash-decoding") contract: grid (Hkv, B, SPLITS); each split
-// takes a contiguous 1/SPLITS of the VALID range [0, seq_lens[b]) (not of
-// Smax: splitting the allocation left the low splits with full spans and
-// the tail split nearly idle), streams it once for all G heads and writes
-// UNNORMALIZED partials to the workspace
+// takes a contiguous 1/SPLITS of the VALID range (not of Smax: splitting
+// the allocation left the low splits with full spans and the tail split
+// nearly idle) and writes UNNORMALIZED partials to the workspace
 //   ws_o  [B, Hkv, SPLITS, G, D]   o = sum exp(s - m) v
 //   ws_ml [B, Hkv, SPLITS, G, 2]   running max m, sum l (m = -inf: empty)
-// which decode_attn_combine_kernel reduces.  SPLITS is chosen to fill the
-// 256 CUs (Hkv*B alone is 0.5 blocks/CU at common shapes).  At SPLITS == 1
-// (the 64-slot continuous-serving shape: B*Hkv already fills the chip) the
-// block normalizes and writes `out` itself — no combine launch, no fp32
-// workspace round-trip.
-// DT: compile-time head dim.  Every inner loop gets a compile-time trip
-// count so the compiler unrolls and BATCHES the global loads — the dynamic
-// version compiled to ONE load + s_waitcnt(0) per iteration (zero
-// memory-level parallelism; measured 87 us where streaming SoL is ~17 us).
-// Phase A loads K rows COOPERATIVELY — a 16-lane group reads one 256 B row
-// per iteration (1 KB coalesced per wave-instruction), each lane dots its
-// 8-dim slice against its loop-invariant register copy of q (8 dims x G
-// heads), group16 shuffles reduce the partials.  Phase B: a thread owns 8
-// dims of every 16th key row (16 B V loads); its partial O accumulates
-// across ALL chunks, rescaled by alpha like the softmax state, and is
-// LDS-reduced once at the end.  ~10 KB LDS, ~170 VGPRs: 3 blocks/CU.
-// Measured dead ends, kept out: staging K through a 64 KB XOR-swizzled LDS
-// tile (2 blocks/CU, PMC wave-state split 48% parked on waits/barriers,
-// 8-13% slower across shapes); a cross-chunk register-pipelined K prefetch
-// (-20%: the in-order vmcnt counter makes later V waits drain it, and the
-// doubled VGPRs halved occupancy).
-template <int G, int DT>
-__launch_bounds__(DEC_CHUNK, 1)
-__global__ void decode_attn_coop_kernel(
-    const bf16* __restrict__ q, const bf16* __restrict__ kc,
-    const bf16* __restrict__ vc,
+// which decode_attn_combine_kernel reduces.  At SPLITS == 1 the block
+// normalizes and writes `out` itself — no combine launch, no fp32
+// workspace round-trip; the wave-private state makes a wider block free, so
+// the launcher (bindings.hip) takes 8 waves instead of 2 splits once
+// B*Hkv fills the chip.
+//
+// FUSED: the q source is the raw QKV projection [B, (H+2*Hkv)*D] and
+// seq_lens[b] is the position `pos` of the new token.  Every lane rotates
+// its own q slice (RoPE at pos; its 8 dims are 4 whole pairs) and rounds
+// it to bf16 exactly as decode_qkv_prep_kernel does, so no q tensor
+// exists.  Keys [0, pos) stream from the cache; the block of the LAST
+// split rotates and rounds the new k, stores the new k/v rows at row pos
+// and seeds wave 0 / group 0's softmax state with that key from
+// registers.  No block reads row pos in this launch, rows < pos are never
+// written.  The rotation is written with explicit fma/mul in the order the
+// prep kernel compiles to, so the stored K row is bit-equal to its.
+//
+// Measured (profiles/README.md "Wave-private decode attention"): isolated,
+// llama3-8b heads, B=32 slen=1600 (210 MB of K+V): 37.4 us = 5.6 TB/s,
+// against 82.0 us for the block-shared kernel before it; B=16: 26 us
+// against 56; B=32 slen=512: 15 us against 41.  In the bench's decode graph
+// the attention chain (prep + attention + combine) went from 68.7 to
+// 24.6 us per layer at batch 32 and from 54.7 to 23.4 us at batch 16.
+// <4,128>: 237 VGPRs (188 fused), no scratch, 2 waves/SIMD at NW 4 and 8 —
+// what one 8-wave block per CU provides anyway; NW=16 would cap a wave at
+// 128 VGPRs and is not instantiated.  KB shrinks with G so that every
+// instantiation stays free of scratch.
+//
+// Measured dead ends, kept out: block-shared softmax state (scores through
+// an LDS p_sh, two block reductions per 256-key chunk: ~6 barriers per
+// chunk, PMC 48% of wave time parked on waits/barriers); staging K through
+// a 64 KB XOR-swizzled LDS tile (2 blocks/CU, 8-13% slower across shapes);
+// a cross-chunk K-only register prefetch (-20%: with V loads between, the
+// in-order vmcnt counter made later V waits drain it, and the doubled
+// VGPRs halved occupancy).
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(
+      0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+// sum within 16-lane rows on the VALU (DPP), result in every lane: xor 1 and
+// xor 2 as quad permutes, then half-row and row mirrors (quads, then
+// halves, already hold equal values, so a mirror acts as xor 4 / xor 8).
+// __shfl_xor would go through the LDS crossbar (ds_bpermute).
+__device__ __forceinline__ float group16_sum_dpp(float v) {
+  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);   // row_half_mirror
+  v += dpp_mov<0x140>(v);   // row_mirror
+  return v;
+}
+__device__ __forceinline__ float fast_exp2(float x) {
+  return __builtin_amdgcn_exp2f(x);       // v_exp_f32; exp2(-inf) = 0
+}
+// RoPE on one lane's 8-dim slice (4 pairs), rounded to bf16 bits.  Same
+// operation order as decode_qkv_prep_kernel's compiled form:
+//   y0 = fma(x0, c, -(x1*sn)),  y1 = fma(x1, c, x0*sn).
+__device__ __forceinline__ bf16x8 rope_slice(bf16x8 x, const float4 c,
+                                             const float4 sn) {
+  const float cc[4] = {c.x, c.y, c.z, c.w};
+  const float ss[4] = {sn.x, sn.y, sn.z, sn.w};
+  bf16x8 y;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x0 = bits2f(x[2 * j]), x1 = bits2f(x[2 * j + 1]);
+    const float y0 = __builtin_fmaf(x0, cc[j], -(x1 * ss[j]));
+    const float y1 = __builtin_fmaf(x1, cc[j], x0 * ss[j]);
+    const bf16 r0 = f2bf(y0), r1 = f2bf(y1);
+    y[2 * j] = (short)__builtin_bit_cast(unsigned short, r0);
+    y[2 * j + 1] = (short)__builtin_bit_cast(unsigned short, r1);
+  }
+  return y;
+}
+
+// keys per group per batch: 2*KB 16-byte loads in flight per lane
+// (sized so q, o, the scores and the batch fit 256 VGPRs without scratch)
+template <int G> struct DecBatch {
+  static constexpr int value = G <= 4 ? 8 : G <= 6 ? 4 : 2;
+};
+
+template <int G, int DT, int NW, bool FUSED>
+__launch_bounds__(NW * WAVE)
+__global__ void decode_attn_kernel(
+    const bf16* __restrict__ qsrc, bf16* kc, bf16* vc,
     float* __restrict__ ws_o, float* __restrict__ ws_ml,
     bf16* __restrict__ out,
+    const float* __restrict__ cosT, const float* __restrict__ sinT,
     const int* __restrict__ seq_lens,
-    int H, int Hkv, int Smax, int D_, float scale, int splits) {
+    int H, int Hkv, int Smax, float scale, int splits) {
   constexpr int D = DT;
   constexpr int ROWB = D / 8;              // lanes that cover one K row
+  constexpr int KB = DecBatch<G>::value;
+  constexpr float LOG2E = 1.4426950408889634f;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* p_sh = reinterpret_cast<float*>(smem);            // [G][DEC_CHUNK]
-  float* q_sh = p_sh + G * DEC_CHUNK;                      // [G][D]
-  float* red = q_sh + G * D;                               // [32] scratch
-  float* o_sh = red + 32;                                  // [G][D]
+  float* sm_o = reinterpret_cast<float*>(smem);            // [NW][G][D]
+  float* sm_ml = sm_o + NW * G * D;                        // [NW][G][2]
 
   const int hkv = blockIdx.x;
   const int b = blockIdx.y;
   const int split = blockIdx.z;
-  const int slen = seq_lens[b];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int li = lane & 15;                // lane-in-group: dim slice owner
+  const int g4 = lane >> 4;                // group in wave: key owner
+  // lanes beyond ROWB (D=64) duplicate a slice and are masked out of the dot
+  const int ls = li % ROWB;
+  const int len_raw = seq_lens[b];
+  const int slen = max(0, min(len_raw, Smax));   // cache rows to stream
   const int span = (slen + splits - 1) / splits;
   const int s_begin = split * span;
   const int s_end = min(slen, s_begin + span);
-  const bf16* kb = kc + ((long)b * Hkv + hkv) * Smax * (long)D;
-  const bf16* vb = vc + ((long)b * Hkv + hkv) * Smax * (long)D;
+  const long cache_off = ((long)b * Hkv + hkv) * Smax * (long)D;
+  const short* kb = reinterpret_cast<const short*>(kc + cache_off) + ls * 8;
+  const short* vb = reinterpret_cast<const short*>(vc + cache_off) + ls * 8;
 
-  for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
-    const int g = i / D, d = i % D;
-    q_sh[i] = bf2f(q[((long)b * H + hkv * G + g) * D + d]);
-    o_sh[i] = 0.f;
+  // ---- q slice: loop-invariant registers, pre-scaled for exp2
+  const int HT = FUSED ? H + 2 * Hkv : H;  // heads per row of qsrc
+  const int pos = max(0, min(len_raw, Smax - 1));
+  float4 rc, rs;
+  if (FUSED) {
+    const long toff = (long)pos * (D / 2) + ls * 4;
+    rc = *reinterpret_cast<const float4*>(cosT + toff);
+    rs = *reinterpret_cast<const float4*>(sinT + toff);
   }
-  __syncthreads();
-
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int li = lane & 15;                // lane-in-group: dim slice owner
-  const int g4 = lane >> 4;                // group in wave: key owner
-  // loop-invariant per-lane q slice (lanes beyond ROWB duplicate a slice
-  // and are masked out of the reduction)
+  const float qs = scale * LOG2E;
   float q_reg[G][8];
 #pragma unroll
-  for (int g = 0; g < G; ++g)
+  for (int g = 0; g < G; ++g) {
+    bf16x8 qv = *reinterpret_cast<const bf16x8*>(
+        qsrc + ((long)b * HT + hkv * G + g) * D + ls * 8);
+    if (FUSED) qv = rope_slice(qv, rc, rs);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-      q_reg[g][e] = q_sh[g * D + (li % ROWB) * 8 + e];
-
-  float m_run[G], l_run[G], alpha[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { m_run[g] = -INFINITY; l_run[g] = 0.f; }
-
-  const int dgroup = threadIdx.x & 15;
-  const int jslot = threadIdx.x >> 4;
-  const bool dg_ok = dgroup < ROWB;
-  float o_part[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o_part[g][e] = 0.f;
-
-  for (int s0 = s_begin; s0 < s_end; s0 += DEC_CHUNK) {
-    const int chunk = min(DEC_CHUNK, s_end - s0);
-    // ---- phase A: cooperative dot.  Wave w owns keys [w*64, w*64+64);
-    // iteration u: group g4 covers key w*64 + u*4 + g4; lane li reads its
-    // 16 B dim slice.  Loads clamp to the valid span (no exec-mask
-    // predication: it forces conservative vmcnt(0) waits); out-of-range
-    // keys are masked in the softmax via row >= chunk.
-    constexpr int AIT = 64 / 4;            // iterations per wave
-    constexpr int ABATCH = 8;              // K rows in flight
-#pragma unroll
-    for (int u0 = 0; u0 < AIT; u0 += ABATCH) {
-      bf16x8 kr[ABATCH];
-#pragma unroll
-      for (int u = 0; u < ABATCH; ++u) {
-        const long key = min((long)(s0 + wid * 64 + (u0 + u) * 4 + g4),
-                             (long)(s_end - 1));
-        kr[u] = nt_load8(reinterpret_cast<const short*>(kb + key * D) +
-                         (li % ROWB) * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < ABATCH; ++u) {
-        float part[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          float acc = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            acc += bits2f(kr[u][e]) * q_reg[g][e];
-          part[g] = (li < ROWB) ? acc : 0.f;
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) part[g] = group16_sum(part[g]);
-        if (li == 0) {
-          const int key_local = wid * 64 + (u0 + u) * 4 + g4;
-#pragma unroll
-          for (int g = 0; g < G; ++g)
-            p_sh[g * DEC_CHUNK + key_local] = part[g] * scale;
-        }
-      }
-    }
-    __syncthreads();                       // scores visible to owners
-
-    // ---- V prefetch, first half (second half issues mid-PV)
-    constexpr int JT = DEC_CHUNK / 16;
-    constexpr int JH = JT / 2;
-    bf16x8 v8[JH];
-    auto load_v = [&](int half) {
-#pragma unroll
-      for (int u = 0; u < JH; ++u) {
-        const long j = min((long)(s0 + jslot + (half * JH + u) * 16),
-                           (long)(s_end - 1));
-        v8[u] = nt_load8(reinterpret_cast<const short*>(vb + j * D) +
-                         dgroup * 8);
-      }
-    };
-    if (dg_ok) load_v(0);
-
-    // ---- softmax (thread-per-key; raw score from p_sh, p written back
-    // in place — each thread touches only its own slot before the
-    // publishing barrier)
-    {
-      const int row = threadIdx.x;
-      float sc[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        sc[g] = (row < chunk) ? p_sh[g * DEC_CHUNK + row] : -INFINITY;
-      float mx[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) mx[g] = sc[g];
-      block_reduce_vec<G, true>(mx, red);
-      float sums[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float m_new = fmaxf(m_run[g], mx[g]);
-        float a = (m_run[g] == -INFINITY) ? 0.f : __expf(m_run[g] - m_new);
-        if (m_new == -INFINITY) a = 1.f;
-        alpha[g] = a;
-        const float p = (sc[g] != -INFINITY) ? __expf(sc[g] - m_new) : 0.f;
-        p_sh[g * DEC_CHUNK + row] = p;
-        sums[g] = p;
-        m_run[g] = m_new;
-      }
-      block_reduce_vec<G, false>(sums, red);  // barrier also publishes p_sh
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        l_run[g] = l_run[g] * alpha[g] + sums[g];
-    }
-
-    // ---- PV consume in two halves
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o_part[g][e] *= alpha[g];
-    if (dg_ok) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        if (half) load_v(1);
-#pragma unroll
-        for (int u = 0; u < JH; ++u) {
-          const int j = jslot + (half * JH + u) * 16;
-          if (j >= chunk) continue;        // p is 0 there anyway
-          float vf[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vf[e] = bits2f(v8[u][e]);
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-            const float p = p_sh[g * DEC_CHUNK + j];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o_part[g][e] += p * vf[e];
-          }
-        }
-      }
-    }
-    __syncthreads();
+    for (int e = 0; e < 8; ++e) q_reg[g][e] = bits2f(qv[e]) * qs;
   }
 
-  if (dg_ok) {
+  float m_run[G], l_run[G], o[G][8];
 #pragma unroll
-    for (int g = 0; g < G; ++g)
+  for (int g = 0; g < G; ++g) {
+    m_run[g] = -INFINITY;
+    l_run[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+  }
+
+  // ---- FUSED: the new token, owned by the last split's block
+  if (FUSED && split == splits - 1) {
+    const bf16* krow = qsrc + ((long)b * HT + H + hkv) * D + ls * 8;
+    bf16x8 kn = rope_slice(*reinterpret_cast<const bf16x8*>(krow), rc, rs);
+    const bf16x8 vn = *reinterpret_cast<const bf16x8*>(krow + (long)Hkv * D);
+    const bool take = wid == 0 && g4 == 0;
+    if (take && li < ROWB && len_raw >= 0 && len_raw < Smax) {
+      const long row = cache_off + (long)len_raw * D + li * 8;
+      *reinterpret_cast<bf16x8*>(kc + row) = kn;
+      *reinterpret_cast<bf16x8*>(vc + row) = vn;
+    }
+    float sn[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float acc = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc += bits2f(kn[e]) * q_reg[g][e];
+      if (ROWB < 16) acc = (li < ROWB) ? acc : 0.f;
+      sn[g] = group16_sum_dpp(acc);
+    }
+    if (take) {                            // p = exp2(s - s) = 1
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        m_run[g] = sn[g];
+        l_run[g] = 1.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] = bits2f(vn[e]);
+      }
+    }
+  }
+
+  // ---- key loop: wave-private, no LDS, no barrier
+  const int nbatch = (s_end - s_begin + 4 * KB - 1) / (4 * KB);
+  for (int t = wid; t < nbatch; t += NW) {
+    const int k0 = s_begin + t * (4 * KB) + g4;
+    bf16x8 kr[KB], vr[KB];
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+      kr[u] = nt_load8(kb + (long)min(k0 + u * 4, s_end - 1) * D);
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+      vr[u] = nt_load8(vb + (long)min(k0 + u * 4, s_end - 1) * D);
+    // keep all 2*KB loads ahead of the first use: left alone, the scheduler
+    // sinks each V load next to its consumer behind a vmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
+
+    float s[KB][G];
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float acc = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc += bits2f(kr[u][e]) * q_reg[g][e];
+        if (ROWB < 16) acc = (li < ROWB) ? acc : 0.f;
+        acc = group16_sum_dpp(acc);
+        s[u][g] = (k0 + u * 4 < s_end) ? acc : -INFINITY;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float mx = s[0][g];
+#pragma unroll
+      for (int u = 1; u < KB; ++u) mx = fmaxf(mx, s[u][g]);
+      const float m_new = fmaxf(m_run[g], mx);
+      const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
+      const float alpha = fast_exp2(m_run[g] - m_safe);
+      m_run[g] = m_new;
+      float l = l_run[g] * alpha;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        const float p = fast_exp2(s[u][g] - m_safe);
+        s[u][g] = p;
+        l += p;
+      }
+      l_run[g] = l;
+    }
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      float vf[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vf[e] = bits2f(vr[u][e]);
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] += s[u][g] * vf[e];
+    }
+  }
+
+  // ---- fold the wave's four groups (same dim slice, different keys)
+#pragma unroll
+  for (int off = 16; off <= 32; off <<= 1) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float mo = __shfl_xor(m_run[g], off, WAVE);
+      const float lo = __shfl_xor(l_run[g], off, WAVE);
+      const float mm = fmaxf(m_run[g], mo);
+      const float ms = (mm == -INFINITY) ? 0.f : mm;
+      const float a = fast_exp2(m_run[g] - ms);
+      const float ao = fast_exp2(mo - ms);
+      l_run[g] = l_run[g] * a + lo * ao;
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        atomicAdd(&o_sh[g * D + dgroup * 8 + e], o_part[g][e]);
+        o[g][e] = o[g][e] * a + __shfl_xor(o[g][e], off, WAVE) * ao;
+      m_run[g] = mm;
+    }
+  }
+
+  // ---- fold the waves through LDS, one barrier
+  if (g4 == 0 && li < ROWB) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float4* dst =
+          reinterpret_cast<float4*>(sm_o + (wid * G + g) * D + li * 8);
+      dst[0] = make_float4(o[g][0], o[g][1], o[g][2], o[g][3]);
+      dst[1] = make_float4(o[g][4], o[g][5], o[g][6], o[g][7]);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      sm_ml[(wid * G + g) * 2 + 0] = m_run[g];
+      sm_ml[(wid * G + g) * 2 + 1] = l_run[g];
+    }
   }
   __syncthreads();
 
-  if (splits == 1) {
-    for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
-      const int g = i / D, d = i % D;
-      const float den = l_run[g] > 0.f ? l_run[g] : 1.f;
-      out[((long)b * H + hkv * G + g) * D + d] = f2bf(o_sh[i] / den);
-    }
-    return;
-  }
   const long base = (((long)b * Hkv + hkv) * splits + split) * G;
-  for (int i = threadIdx.x; i < G * D; i += blockDim.x) {
+  for (int i = threadIdx.x; i < G * D; i += NW * WAVE) {
     const int g = i / D, d = i % D;
-    ws_o[(base + g) * D + d] = o_sh[i];
-  }
-  if (threadIdx.x == 0) {
+    float M = -INFINITY;
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-      ws_ml[(base + g) * 2 + 0] = m_run[g];
-      ws_ml[(base + g) * 2 + 1] = l_run[g];
+    for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_ml[(w * G + g) * 2]);
+    const float ms = (M == -INFINITY) ? 0.f : M;
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const float a = fast_exp2(sm_ml[(w * G + g) * 2] - ms);
+      den += sm_ml[(w * G + g) * 2 + 1] * a;
+      num += sm_o[(w * G + g) * D + d] * a;
+    }
+    if (splits == 1) {
+      out[((long)b * H + hkv * G + g) * D + d] =
+          f2bf(den > 0.f ? num / den : 0.f);
+    } else {
+      ws_o[(base + g) * D + d] = num;
+      if (d == 0) {                        // m back in natural-log units
+        ws_ml[(base + g) * 2 + 0] = M * (1.f / LOG2E);
+        ws_ml[(base + g) * 2 + 1] = den;
+      }
     }
   }
 }
@@ -586,6 +682,56 @@ __global__ void decode_attn_combine_kernel(
     }
     out[((long)b * H + h) * D + d] = f2bf(num / den);
   }
+}
+
+// One launcher for both decode entry points: FUSED picks the q source and
+// the append step.  waves is the block width (4 or 8); workspaces are only
+// touched when splits > 1.
+template <bool FUSED>
+static hipError_t launch_decode_attn(const void* qsrc, void* kc, void* vc,
+                                     void* out, const float* cosT,
+                                     const float* sinT, const int* seq_lens,
+                                     float* ws_o, float* ws_ml, int splits,
+                                     int waves, int B, int H, int Hkv,
+                                     int Smax, int D, float scale,
+                                     hipStream_t stream) {
+  if (Hkv < 1 || H < 1 || H % Hkv || Smax < 1 || B < 1 || splits < 1 ||
+      (D & 1) || (D != 64 && D != 128) || (waves != 4 && waves != 8))
+    return hipErrorInvalidValue;
+  const int G = H / Hkv;
+  if (G > DEC_MAXG) return hipErrorInvalidValue;
+  if (splits > 1 && (!ws_o || !ws_ml)) return hipErrorInvalidValue;
+  // sm_o [NW][G][D] | sm_ml [NW][G][2]
+  const size_t lds = (size_t)waves * (G * D + 2 * G) * sizeof(float);
+  dim3 grid(Hkv, B, splits);
+#define DEC_LAUNCH(GV, DV, NWV)                                               \
+  hipLaunchKernelGGL((decode_attn_kernel<GV, DV, NWV, FUSED>), grid,          \
+                     dim3(NWV * WAVE), lds, stream, (const bf16*)qsrc,        \
+                     (bf16*)kc, (bf16*)vc, ws_o, ws_ml, (bf16*)out, cosT,     \
+                     sinT, seq_lens, H, Hkv, Smax, scale, splits)
+#define DEC_CASE(GV, DV)                                                      \
+  case GV * 1000 + DV:                                                        \
+    if (waves == 8) DEC_LAUNCH(GV, DV, 8);                                    \
+    else DEC_LAUNCH(GV, DV, 4);                                               \
+    break;
+#define DEC_ALL_G(DV)                                                 \
+  DEC_CASE(1, DV) DEC_CASE(2, DV) DEC_CASE(3, DV) DEC_CASE(4, DV)     \
+  DEC_CASE(5, DV) DEC_CASE(6, DV) DEC_CASE(7, DV) DEC_CASE(8, DV)
+  switch (G * 1000 + D) {
+    DEC_ALL_G(64) DEC_ALL_G(128)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef DEC_ALL_G
+#undef DEC_CASE
+#undef DEC_LAUNCH
+  HIP_CHECK_LAUNCH();
+  if (splits > 1) {   // splits==1 normalized + wrote out in the decode kernel
+    hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(H, B), dim3(128), 0,
+                       stream, ws_o, ws_ml, (bf16*)out, H, G, D, splits);
+    HIP_CHECK_LAUNCH();
+  }
+  return hipSuccess;
 }
 
 // One launcher for both prefill entry points: CACHE_SRC picks the K/V
@@ -639,39 +785,25 @@ hipError_t sentio_flash_attn_cache(const void* q, const void* kc,
 
 hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
                               void* out, const int* seq_lens,
-                              float* ws_o, float* ws_ml, int splits,
+                              float* ws_o, float* ws_ml, int splits, int waves,
                               int B, int H, int Hkv, int Smax, int D,
                               float scale, hipStream_t stream) {
-  const int G = H / Hkv;
-  if (H % Hkv || G > DEC_MAXG || (D != 64 && D != 128))
-    return hipErrorInvalidValue;
-  // p_sh [G][DEC_CHUNK] | q_sh [G][D] | red [32] | o_sh [G][D]
-  const size_t lds = (size_t)(G * DEC_CHUNK + 2 * G * D + 32) * sizeof(float);
-  dim3 grid(Hkv, B, splits);
-#define DEC_CASE(GV, DV)                                                      \
-  case GV * 1000 + DV:                                                        \
-    hipLaunchKernelGGL((decode_attn_coop_kernel<GV, DV>), grid,               \
-                       dim3(DEC_CHUNK), lds, stream, (const bf16*)q,          \
-                       (const bf16*)kc, (const bf16*)vc, ws_o, ws_ml,         \
-                       (bf16*)out, seq_lens, H, Hkv, Smax, D, scale, splits); \
-    break;
-#define DEC_ALL_G(DV)                                                 \
-  DEC_CASE(1, DV) DEC_CASE(2, DV) DEC_CASE(3, DV) DEC_CASE(4, DV)     \
-  DEC_CASE(5, DV) DEC_CASE(6, DV) DEC_CASE(7, DV) DEC_CASE(8, DV)
-  switch (G * 1000 + D) {
-    DEC_ALL_G(64) DEC_ALL_G(128)
-    default:   // G < 1
-      return hipErrorInvalidValue;
-  }
-#undef DEC_ALL_G
-#undef DEC_CASE
-  HIP_CHECK_LAUNCH();
-  if (splits > 1) {   // splits==1 normalized + wrote out in the decode kernel
-    hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(H, B), dim3(128), 0,
-                       stream, ws_o, ws_ml, (bf16*)out, H, G, D, splits);
-    HIP_CHECK_LAUNCH();
-  }
-  return hipSuccess;
+  return launch_decode_attn<false>(q, const_cast<void*>(kc),
+                                   const_cast<void*>(vc), out, nullptr,
+                                   nullptr, seq_lens, ws_o, ws_ml, splits,
+                                   waves, B, H, Hkv, Smax, D, scale, stream);
+}
+
+hipError_t sentio_decode_attn_fused(const void* qkv, void* kc, void* vc,
+                                    void* out, const float* cosT,
+                                    const float* sinT, const int* seq_lens,
+                                    float* ws_o, float* ws_ml, int splits,
+                                    int waves, int B, int H, int Hkv,
+                                    int Smax, int D, float scale,
+                                    hipStream_t stream) {
+  return launch_decode_attn<true>(qkv, kc, vc, out, cosT, sinT, seq_lens,
+                                  ws_o, ws_ml, splits, waves, B, H, Hkv, Smax,
+                                  D, scale, stream);
 }
 
 }  // extern "C"

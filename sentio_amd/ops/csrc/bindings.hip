@@ -7,6 +7,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <tuple>
 
 #include "sentio_kernels.h"
 
@@ -260,32 +261,111 @@ torch::Tensor flash_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   return out;
 }
 
+// Launch policy of the decode-attention kernel: (splits, waves per block).
+// Once B*Hkv blocks fill the 256 CUs, one 8-wave block per (b, kv-head)
+// streams the whole row and writes bf16 output itself: no workspace, no
+// combine launch.  Below that, split-S across 4-wave blocks so the grid
+// reaches >= 2 blocks per CU.  SENTIO_DECODE_SPLITS (clamped to one split
+// per 256 cache rows) and SENTIO_DECODE_WAVES (4 or 8) override either
+// half for probes and tests.
+std::tuple<int, int> decode_attn_plan(long B, long Hkv, long Smax) {
+  TORCH_CHECK(B > 0 && Hkv > 0 && Smax > 0, "decode_attn_plan: empty shape");
+  const long blocks = B * Hkv;
+  const int max_splits = (int)std::max(1L, Smax / 256);
+  int splits = 1, waves = 8;
+  if (blocks < 256) {
+    splits = (int)std::max(1L, std::min((512 + blocks - 1) / blocks,
+                                        (long)max_splits));
+    waves = 4;
+  }
+  if (const char* ov = std::getenv("SENTIO_DECODE_SPLITS"))
+    splits = std::max(1, std::min(atoi(ov), max_splits));
+  if (const char* ov = std::getenv("SENTIO_DECODE_WAVES")) {
+    waves = atoi(ov);
+    TORCH_CHECK(waves == 4 || waves == 8,
+                "SENTIO_DECODE_WAVES must be 4 or 8, got '", ov, "'");
+  }
+  return {splits, waves};
+}
+
+// fp32 split-S partials; empty when the decode kernel writes `out` itself
+struct DecodeWorkspace {
+  torch::Tensor o, ml;
+  float* o_ptr = nullptr;
+  float* ml_ptr = nullptr;
+  DecodeWorkspace(const torch::Tensor& like, int splits, long B, long Hkv,
+                  long G, long D) {
+    if (splits <= 1) return;
+    const long n = B * Hkv * splits * G;
+    o = torch::empty({n * D}, like.options().dtype(torch::kFloat));
+    ml = torch::empty({n * 2}, like.options().dtype(torch::kFloat));
+    o_ptr = o.data_ptr<float>();
+    ml_ptr = ml.data_ptr<float>();
+  }
+};
+
+void check_caches(const torch::Tensor& kc, const torch::Tensor& vc) {
+  check_bf16_cuda(kc, "k cache");
+  check_bf16_cuda(vc, "v cache");
+  TORCH_CHECK(kc.dim() == 4, "k cache must be [B,Hkv,Smax,D]");
+  TORCH_CHECK(vc.sizes() == kc.sizes(), "k and v cache shapes differ");
+}
+
 torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                           torch::Tensor seq_lens, double scale) {
   check_bf16_cuda(q, "q");
   TORCH_CHECK(q.dim() == 3, "q must be [B,H,D]");
-  TORCH_CHECK(kc.dim() == 4, "k cache must be [B,Hkv,Smax,D]");
+  check_caches(kc, vc);
   const int B = q.size(0), H = q.size(1), D = q.size(2);
   const int Hkv = kc.size(1), Smax = kc.size(2);
-  const int G = H / Hkv;
+  TORCH_CHECK(kc.size(0) >= B && kc.size(3) == D, "cache/q shape mismatch");
   auto out = torch::empty_like(q);
   auto sl = seq_lens.to(torch::kInt).contiguous();
-  // split-S so the grid fills the chip: target >= 2 blocks per CU
-  int splits = (int)((512 + (long)B * Hkv - 1) / ((long)B * Hkv));
-  int max_splits = std::max(1, Smax / 256);
-  splits = std::max(1, std::min(splits, max_splits));
-  if (const char* ov = std::getenv("SENTIO_DECODE_SPLITS"))
-    splits = std::max(1, std::min(atoi(ov), max_splits));
-  // splits==1 writes `out` directly from the decode kernel (no combine):
-  // keep only dummy workspaces
-  const long ws_n = splits > 1 ? (long)B * Hkv * splits * G : 1;
-  auto ws_o = torch::empty({ws_n * D}, q.options().dtype(torch::kFloat));
-  auto ws_ml = torch::empty({ws_n * 2}, q.options().dtype(torch::kFloat));
+  const auto [splits, waves] = decode_attn_plan(B, Hkv, Smax);
+  DecodeWorkspace ws(q, splits, B, Hkv, H / Hkv, D);
   check_hip(sentio_decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                               out.data_ptr(), sl.data_ptr<int>(),
-                               ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(),
-                               splits, B, H, Hkv, Smax, D, (float)scale,
-                               stream()), "decode_attn");
+                               out.data_ptr(), sl.data_ptr<int>(), ws.o_ptr,
+                               ws.ml_ptr, splits, waves, B, H, Hkv, Smax, D,
+                               (float)scale, stream()), "decode_attn");
+  return out;
+}
+
+// Decode attention with decode_qkv_prep folded in: RoPE(q) stays in
+// registers, the new k/v row is written at seq_lens[b] and attended from
+// registers; covers seq_lens[b] + 1 keys.
+torch::Tensor decode_attn_fused(torch::Tensor qkv, torch::Tensor kc,
+                                torch::Tensor vc, torch::Tensor cosT,
+                                torch::Tensor sinT, torch::Tensor seq_lens,
+                                double scale) {
+  check_bf16_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (H+2*Hkv)*D]");
+  check_caches(kc, vc);
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == torch::kInt &&
+              seq_lens.is_contiguous(),
+              "seq_lens must be a contiguous i32 GPU tensor");
+  const int B = qkv.size(0);
+  const int Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
+  const int H = (int)(qkv.size(1) / D) - 2 * Hkv;
+  TORCH_CHECK(H > 0 && H % Hkv == 0 &&
+              (long)(H + 2 * Hkv) * D == qkv.size(1), "qkv width mismatch");
+  TORCH_CHECK(kc.size(0) >= B && seq_lens.numel() == B,
+              "batch mismatch between qkv, caches and seq_lens");
+  for (const auto* t : {&cosT, &sinT}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                t->is_contiguous() && t->dim() == 2 && t->size(0) >= Smax &&
+                t->size(1) == D / 2,
+                "rope tables must be contiguous f32 [>=Smax, D/2] on GPU");
+  }
+  auto out = torch::empty({B, H, D}, qkv.options());
+  const auto [splits, waves] = decode_attn_plan(B, Hkv, Smax);
+  DecodeWorkspace ws(qkv, splits, B, Hkv, H / Hkv, D);
+  check_hip(sentio_decode_attn_fused(
+                qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                cosT.data_ptr<float>(), sinT.data_ptr<float>(),
+                seq_lens.data_ptr<int>(), ws.o_ptr, ws.ml_ptr, splits, waves,
+                B, H, Hkv, Smax, D, (float)scale, stream()),
+            "decode_attn_fused");
   return out;
 }
 
@@ -383,6 +463,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_cache", &flash_attn_cache);
   m.def("decode_attn", &decode_attn);
+  m.def("decode_attn_fused", &decode_attn_fused);
+  m.def("decode_attn_plan", &decode_attn_plan);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("fuse_topk", &fuse_topk);

@@ -80,12 +80,23 @@ hipError_t sentio_flash_attn_cache(const void* q, const void* kc,
                                    const int* kv_lens, int B, int S, int H,
                                    int Hkv, int Smax, int D, float scale,
                                    int q_off, hipStream_t stream);
-// splits comes BEFORE the shape; no S (one query token per row)
+// splits and waves (block width, 4 or 8) come BEFORE the shape; no S (one
+// query token per row); ws_o/ws_ml may be null when splits == 1
 hipError_t sentio_decode_attn(const void* q, const void* kc, const void* vc,
                               void* out, const int* seq_lens, float* ws_o,
-                              float* ws_ml, int splits, int B, int H, int Hkv,
-                              int Smax, int D, float scale,
+                              float* ws_ml, int splits, int waves, int B,
+                              int H, int Hkv, int Smax, int D, float scale,
                               hipStream_t stream);
+// as sentio_decode_attn, but the first argument is the raw QKV projection
+// [B, (H+2*Hkv)*D], the caches are WRITTEN (row seq_lens[b]), and the RoPE
+// tables sit between out and seq_lens; seq_lens is the new token's position
+hipError_t sentio_decode_attn_fused(const void* qkv, void* kc, void* vc,
+                                    void* out, const float* cosT,
+                                    const float* sinT, const int* seq_lens,
+                                    float* ws_o, float* ws_ml, int splits,
+                                    int waves, int B, int H, int Hkv,
+                                    int Smax, int D, float scale,
+                                    hipStream_t stream);
 
 // ---- gemm.hip / blaslt.hip
 // B is [K, N] row-major; dims are (M, N, K)

@@ -306,6 +306,18 @@ def decode_qkv_prep(
     return q.view(B, H, D)
 
 
+def decode_attention_fused(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor,
+    scale: float | None = None,
+) -> torch.Tensor:
+    """CPU reference of ops.decode_attention_fused: decode_qkv_prep (writes
+    the k/v row at seq_lens[b]) followed by decode_attention over
+    seq_lens[b] + 1 keys."""
+    q = decode_qkv_prep(qkv, k_cache, v_cache, cos, sin, seq_lens)
+    return decode_attention(q, k_cache, v_cache, seq_lens + 1, scale)
+
+
 def swiglu_packed(gu: torch.Tensor) -> torch.Tensor:
     """gu [..., 2F] rows packed [gate | up] → silu(gate) * up, [..., F]."""
     f = gu.shape[-1] // 2
