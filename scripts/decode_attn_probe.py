@@ -2,7 +2,11 @@
 Prints achieved µs + effective KV TB/s per (splits, waves) setting for
 ops.decode_attention, for the two-op chain decode_qkv_prep + decode_attention
 and for the one-launch ops.decode_attention_fused.
-Run: python scripts/decode_attn_probe.py [--repeats N] [--main-only]"""
+Run: python scripts/decode_attn_probe.py [--repeats N] [--main-only]
+     python scripts/decode_attn_probe.py --kv fp8 [--repeats N]
+--kv fp8 times ops.decode_attention_fused_fp8 (uint8 e4m3fn caches) beside
+the bf16 ops.decode_attention_fused on the same three shapes, alternating
+the two inside every repeat."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -72,6 +76,55 @@ def main(repeats=1):
 
 
 
+def kv_fp8_probe(repeats=3):
+    """FP8-cache fused decode kernel against the bf16 fused kernel: same
+    shapes, same launch plan; effective TB/s counts each kernel's own KV
+    bytes."""
+    if not torch.cuda.is_available():
+        print(f"{__file__}: needs a GPU (MI355X) — skipping")
+        return
+    dev = "cuda:0"
+    for B, slen in [(16, 1600), (32, 1600), (32, 512)]:
+        H, Hkv, Smax, D = 32, 8, 2120, 128
+        torch.manual_seed(0)
+        qkv = torch.randn(B, (H + 2 * Hkv) * D, dtype=torch.bfloat16,
+                          device=dev)
+        kc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
+        vc = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
+        ones = torch.ones(Hkv, device=dev)
+        kc8 = torch.zeros(B, Hkv, Smax, D, dtype=torch.uint8, device=dev)
+        vc8 = torch.zeros_like(kc8)
+        ops.kv_store_fp8(kc, vc, kc8, vc8, list(range(B)), Smax, ones, ones)
+        cos, sin = ops.torch_ref.rope_tables(Smax, D, device=dev)
+        pos = torch.full((B,), slen - 1, dtype=torch.int32, device=dev)
+        elems = 2 * B * Hkv * slen * D
+        print(f"--- B={B} slen={slen} (KV bf16 {2*elems/1e6:.0f} MB, "
+              f"fp8 {elems/1e6:.0f} MB)")
+
+        def bf16():
+            ops.decode_attention_fused(qkv, kc, vc, cos, sin, pos)
+
+        def fp8():
+            ops.decode_attention_fused_fp8(qkv, kc8, vc8, cos, sin, pos,
+                                           ones, ones, ones, ones)
+
+        for waves, splits in ((0, 0), (4, 0), (8, 1), (4, 2), (4, 4)):
+            setenv("SENTIO_DECODE_WAVES", waves)
+            setenv("SENTIO_DECODE_SPLITS", splits)
+            tb, t8 = [], []
+            for _ in range(repeats):        # alternate the two versions
+                tb.append(bench(bf16))
+                t8.append(bench(fp8))
+            for name, ts, nbytes in (("fused bf16", tb, 2 * elems),
+                                     ("fused fp8 ", t8, elems)):
+                print(f"waves={waves or 'auto'} splits={splits or 'auto'} "
+                      f"{name}: "
+                      + " ".join(f"{t*1e6:7.1f}" for t in ts)
+                      + f" us  {nbytes/min(ts)/1e12:.2f} TB/s")
+        setenv("SENTIO_DECODE_WAVES", 0)
+        setenv("SENTIO_DECODE_SPLITS", 0)
+
+
 def bmm_probe():
     """Compare the hand decode-attention kernel against a batched-GEMM
     formulation (rocBLAS bmm): scores = Q·K^T and O = P·V per (b, kv-head)
@@ -135,6 +188,12 @@ def flash_probe():
 if __name__ == "__main__":
     reps = int(sys.argv[sys.argv.index("--repeats") + 1]) \
         if "--repeats" in sys.argv else 1
+    if "--kv" in sys.argv:
+        kv = sys.argv[sys.argv.index("--kv") + 1]
+        if kv != "fp8":
+            sys.exit(f"--kv takes fp8, got {kv!r}")
+        kv_fp8_probe(max(reps, 3))
+        sys.exit(0)
     main(reps)
     if "--main-only" not in sys.argv:
         bmm_probe()

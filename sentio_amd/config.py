@@ -102,6 +102,7 @@ class Settings:
     tp_degree: int = 1
     index_shards: int = 1                   # = world size when distributed
     kv_cache_max_tokens: int = 8192
+    kv_cache_dtype: str = "bf16"            # bf16 | fp8 (e4m3fn session KV cache)
     max_batch_size: int = 64          # continuous-batching slots (64 rows of KV ~ 68 GB at 8k ctx)
     dynamic_batching: bool = True           # batch concurrent /chat generations
     continuous_batching: bool = True        # requests join decode mid-flight
@@ -153,6 +154,7 @@ class Settings:
         "tp_degree": "TP_DEGREE",
         "index_shards": "INDEX_SHARDS",
         "kv_cache_max_tokens": "KV_CACHE_MAX_TOKENS",
+        "kv_cache_dtype": "KV_CACHE_DTYPE",
         "max_batch_size": "MAX_BATCH_SIZE",
         "dynamic_batching": "DYNAMIC_BATCHING",
         "continuous_batching": "CONTINUOUS_BATCHING",
@@ -181,6 +183,9 @@ class Settings:
                 setattr(s, f.name, _env_float(env, cur))
             else:
                 setattr(s, f.name, _env_str(env, cur))
+        if s.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError("KV_CACHE_DTYPE must be bf16 or fp8, got "
+                             f"{s.kv_cache_dtype!r}")
         return s
 
     @property

@@ -20,7 +20,8 @@ from sentio_amd import ops
 from sentio_amd.engines.configs import get_model_config
 from sentio_amd.engines.bpe import get_tokenizer
 from sentio_amd.engines.tokenizer import EOS_ID
-from sentio_amd.engines.transformer import KVCache, Transformer
+from sentio_amd.engines.transformer import (KVCache, Transformer,
+                                            check_kv_dtype, write_kv_scales)
 
 MODE_TEMPERATURE = {"fast": 0.0, "balanced": 0.3, "quality": 0.2, "creative": 0.7}
 
@@ -60,7 +61,17 @@ class _DecodeSession:
     def prefill(self, tokens: torch.Tensor,
                 lens: torch.Tensor | None = None) -> torch.Tensor:
         self.cache.seq_lens.zero_()
-        return self.engine.model.prefill(tokens, self.cache, lens=lens)
+        engine = self.engine
+        if not self.cache.fp8:
+            return engine.model.prefill(tokens, self.cache, lens=lens)
+        # FP8 session: prompt attention sees exact K/V in a staging cache
+        # exactly as long as the prompt; only decode reads quantised rows
+        B, S = tokens.shape
+        stage = engine._staging_cache(B, S)
+        logits = engine.model.prefill(tokens, stage, lens=lens)
+        engine._splice_kv(self.cache, list(range(B)), stage.k, stage.v, S)
+        self.cache.seq_lens.copy_(stage.seq_lens)
+        return logits
 
     def prefill_with_prefix(self, prefix_ids: list[int],
                             suffix_tokens: torch.Tensor,
@@ -72,11 +83,19 @@ class _DecodeSession:
         engine = self.engine
         pk, pv = engine._prefix_kv(tuple(prefix_ids))
         P = len(prefix_ids)
+        B, S = suffix_tokens.shape
+        # FP8 session: prefix + suffix go through a staging cache of P+S
+        dst = engine._staging_cache(B, P + S) if self.cache.fp8 \
+            else self.cache
         for i in range(engine.cfg.n_layers):
-            self.cache.k[i][:, :, :P].copy_(pk[i])   # [1,...] broadcasts
-            self.cache.v[i][:, :, :P].copy_(pv[i])
-        return engine.model.prefill_suffix(suffix_tokens, self.cache, P,
-                                           suffix_lens=suffix_lens)
+            dst.k[i][:, :, :P].copy_(pk[i])   # [1,...] broadcasts
+            dst.v[i][:, :, :P].copy_(pv[i])
+        logits = engine.model.prefill_suffix(suffix_tokens, dst, P,
+                                             suffix_lens=suffix_lens)
+        if dst is not self.cache:
+            engine._splice_kv(self.cache, list(range(B)), dst.k, dst.v, P + S)
+            self.cache.seq_lens.copy_(dst.seq_lens)
+        return logits
 
     def _capture(self):
         model = self.engine.model
@@ -120,13 +139,30 @@ class _DecodeSession:
 class GeneratorEngine:
     def __init__(self, model: str = "llama3-8b", device: str = "cpu",
                  dtype: str = "bf16", max_seq: int = 4096, seed: int = 303,
-                 tp=None):
+                 tp=None, kv_cache_dtype: str = "bf16"):
         self.cfg = get_model_config(model)
+        # "fp8": session caches hold e4m3fn bytes (half the HBM and half the
+        # bytes a decode step streams); prefill and the prefix store stay in
+        # the model dtype.  Raises here for a model the FP8 kernel cannot
+        # serve, not at the first step.
+        self.kv_cache_dtype = check_kv_dtype(kv_cache_dtype, self.cfg)
         self.device = device
         self.max_seq = min(max_seq, self.cfg.max_seq)
         self.tokenizer = get_tokenizer()
         self.model = Transformer(self.cfg, device=device, dtype=dtype,
                                  seed=seed, tp=tp)
+        if self.kv_cache_dtype == "fp8" and device != "cpu" \
+                and self.model.dtype != torch.bfloat16:
+            raise ValueError("the fp8 KV cache needs a bf16 model on the GPU")
+        # one set of static scales, [4, Hkv] per layer (k_scale, v_scale and
+        # their reciprocals), shared by every session cache: set_kv_scales
+        # updates them in place, captured decode graphs read the new values
+        self._kv_scales = None
+        if self.kv_cache_dtype == "fp8":
+            self._kv_scales = [
+                torch.ones(4, self.model.hkv_local, dtype=torch.float32,
+                           device=device)
+                for _ in range(self.cfg.n_layers)]
         self._step_seed = 0
         self._derived_seeds = 0     # derive_seed()'s own counter
         import threading
@@ -134,8 +170,83 @@ class GeneratorEngine:
         self._gen_lock = threading.Lock()   # decode sessions hold static state
 
     def _new_cache(self, batch: int, max_seq: int) -> KVCache:
+        """A session cache, in the engine's KV dtype."""
+        return KVCache(self.cfg, batch, max_seq, self.device, self.model.dtype,
+                       n_kv_heads=self.model.hkv_local,
+                       kv_dtype=self.kv_cache_dtype, scales=self._kv_scales)
+
+    def _staging_cache(self, batch: int, max_seq: int) -> KVCache:
+        """A prefill target in the model dtype, whatever the KV dtype."""
         return KVCache(self.cfg, batch, max_seq, self.device, self.model.dtype,
                        n_kv_heads=self.model.hkv_local)
+
+    def _splice_kv(self, cache: KVCache, rows: list[int], src_k: list,
+                   src_v: list, S: int, sel: torch.Tensor | None = None
+                   ) -> None:
+        """Copy the first S rows of per-layer staging K/V [n, Hkv, >=S, D]
+        into cache rows `rows`: an index copy for a bf16 cache, the
+        quantising ops.kv_store_fp8 for an fp8 one.  `sel` picks a subset
+        of the staging batch."""
+        if cache.fp8:
+            B = cache.k[0].shape[0]
+            if any(r < 0 or r >= B for r in rows) \
+                    or len(set(rows)) != len(rows):
+                raise ValueError(f"bad cache rows {rows} for batch {B}")
+            rows_t = torch.tensor(rows, dtype=torch.int32, device=self.device)
+        else:
+            rows_t = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        for li in range(self.cfg.n_layers):
+            k, v = src_k[li], src_v[li]
+            if sel is not None:
+                k, v = k[sel], v[sel]
+            if cache.fp8:
+                sc = cache.scales[li]
+                ops.kv_store_fp8(k, v, cache.k[li], cache.v[li], rows_t, S,
+                                 sc[2], sc[3])
+            else:
+                cache.k[li][rows_t, :, :S] = k[:, :, :S]
+                cache.v[li][rows_t, :, :S] = v[:, :, :S]
+
+    # ----- FP8 KV cache: scales -----
+    @property
+    def kv_bytes_per_token(self) -> int:
+        """KV-cache bytes one token occupies on this device, for the
+        engine's KV dtype at its serving width (bf16: 2 bytes, fp8: 1; a CPU
+        engine's fp32 stand-in tensors are not what is reported)."""
+        width = 1 if self.kv_cache_dtype == "fp8" else 2
+        return (2 * self.cfg.n_layers * self.model.hkv_local
+                * self.cfg.head_dim * width)
+
+    def set_kv_scales(self, k_scales, v_scales) -> None:
+        """Per-layer [Hkv] K and V scales of the fp8 cache, updated in place
+        with their reciprocals; no decode graph needs recapturing."""
+        if self._kv_scales is None:
+            raise ValueError("kv scales exist only with kv_cache_dtype='fp8'")
+        with self._gen_lock:
+            write_kv_scales(self._kv_scales, k_scales, v_scales)
+
+    @torch.inference_mode()
+    def calibrate_kv_scales(self, prompts: list[str], margin: float = 2.0):
+        """Static scales from a bf16 prefill of `prompts`: per layer and kv
+        head, scale = max(amax * margin / 448, 2**-20) for K and for V.
+        Sets them (set_kv_scales) and returns (k_scales, v_scales)."""
+        if self._kv_scales is None:
+            raise ValueError("kv scales exist only with kv_cache_dtype='fp8'")
+        if not prompts:
+            raise ValueError("calibration needs at least one prompt")
+        with self._gen_lock:
+            pre = self.prefill_admission(prompts, [1] * len(prompts))
+        tmp, S = pre["tmp"], pre["S"]
+        valid = (torch.arange(S, device=self.device)[None, :]
+                 < pre["lens"][:, None])[:, None, :, None]
+        ks, vs = [], []
+        for li in range(self.cfg.n_layers):
+            for src, dst in ((tmp.k[li], ks), (tmp.v[li], vs)):
+                amax = (src.float().abs() * valid).amax(dim=(0, 2, 3))
+                dst.append((amax * (float(margin) / 448.0))
+                           .clamp_min(2.0 ** -20).cpu())
+        self.set_kv_scales(ks, vs)
+        return ks, vs
 
     # ----- prefix-KV cache (shared prompt prefixes prefilled once) -----
     _PREFIX_MIN_TOKENS = 64
@@ -173,8 +284,7 @@ class GeneratorEngine:
         if hit is not None:
             return hit
         P = len(prefix_ids)
-        tmp = KVCache(self.cfg, 1, P, self.device, self.model.dtype,
-                      n_kv_heads=self.model.hkv_local)
+        tmp = self._staging_cache(1, P)
         toks = torch.tensor([list(prefix_ids)], dtype=torch.int64,
                             device=self.device)
         self.model.forward_hidden(toks, cache=tmp)
@@ -248,8 +358,7 @@ class GeneratorEngine:
         padded = [i + [0] * (S - len(i)) for i in ids_list]
         tokens = torch.tensor(padded, dtype=torch.int64, device=self.device)
         lens_t = torch.tensor(lens, dtype=torch.int32, device=self.device)
-        tmp = KVCache(self.cfg, len(prompts), S, self.device,
-                      self.model.dtype, n_kv_heads=self.model.hkv_local)
+        tmp = self._staging_cache(len(prompts), S)
         logits = self.model.prefill(tokens, tmp, lens=lens_t)
         return {"tmp": tmp, "lens": lens_t, "logits": logits, "S": S,
                 "lens_host": lens}
@@ -267,16 +376,12 @@ class GeneratorEngine:
         logits = pre["logits"]
         with self._gen_lock:
             rows_t = torch.tensor(rows, dtype=torch.int64, device=self.device)
+            sel = None
             if idx is not None:
                 sel = torch.tensor(idx, dtype=torch.int64, device=self.device)
                 lens_t = lens_t[sel]
                 logits = logits[sel]
-            for li in range(self.cfg.n_layers):
-                src_k, src_v = tmp.k[li], tmp.v[li]
-                if idx is not None:
-                    src_k, src_v = src_k[sel], src_v[sel]
-                sess.cache.k[li][rows_t, :, :S] = src_k
-                sess.cache.v[li][rows_t, :, :S] = src_v
+            self._splice_kv(sess.cache, rows, tmp.k, tmp.v, S, sel=sel)
             sess.cache.seq_lens[rows_t] = lens_t
         return logits
 

@@ -107,22 +107,98 @@ class TransformerWeights:
         return total * self.tok_emb.element_size()
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
+def check_kv_dtype(kv_dtype: str, cfg: ModelConfig | None = None) -> str:
+    """Validate a KV-cache dtype name, and for "fp8" that the model fits the
+    FP8 decode kernel — raised where the cache or engine is BUILT, not at
+    the first decode step."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv cache dtype must be one of {KV_DTYPES}, "
+                         f"got {kv_dtype!r}")
+    if kv_dtype == "fp8" and cfg is not None:
+        if os.environ.get("SENTIO_DECODE_ATTN") == "bmm":
+            raise ValueError("the fp8 KV cache has no bmm decode variant "
+                             "(unset SENTIO_DECODE_ATTN=bmm)")
+        if cfg.head_dim not in (64, 128):
+            raise ValueError("the fp8 KV cache needs head dim 64 or 128, "
+                             f"got {cfg.head_dim}")
+        g = cfg.n_heads // cfg.n_kv_heads    # TP shards both alike
+        if g > 8:
+            raise ValueError("the fp8 KV cache serves at most 8 query heads "
+                             f"per kv head, got {g}")
+    return kv_dtype
+
+
 class KVCache:
+    """Contiguous [B, Hkv, Smax, hd] K and V per layer.  kv_dtype "bf16"
+    stores `dtype`; "fp8" stores uint8 e4m3fn bytes (view as
+    torch.float8_e4m3fn) plus static fp32 scales per layer and kv head:
+    scales[layer] is [4, Hkv] = k_scale, v_scale, k_inv, v_inv, read by the
+    kernels at run time — set_scales() updates them in place, captured
+    graphs keep working."""
+
     def __init__(self, cfg: ModelConfig, batch: int, max_seq: int, device: str,
-                 dtype: torch.dtype, n_kv_heads: int | None = None):
+                 dtype: torch.dtype, n_kv_heads: int | None = None,
+                 kv_dtype: str = "bf16", scales: list | None = None):
         nkv = n_kv_heads or cfg.n_kv_heads
+        self.kv_dtype = check_kv_dtype(kv_dtype, cfg)
+        self.fp8 = kv_dtype == "fp8"
+        store = torch.uint8 if self.fp8 else dtype
         self.k = [
             torch.zeros(batch, nkv, max_seq, cfg.head_dim,
-                        dtype=dtype, device=device)
+                        dtype=store, device=device)
             for _ in range(cfg.n_layers)
         ]
         self.v = [
             torch.zeros(batch, nkv, max_seq, cfg.head_dim,
-                        dtype=dtype, device=device)
+                        dtype=store, device=device)
             for _ in range(cfg.n_layers)
         ]
         self.seq_lens = torch.zeros(batch, dtype=torch.int32, device=device)
         self.max_seq = max_seq
+        # `scales` shares another owner's tensors (an engine keeps one set
+        # for all its session caches)
+        self.scales = None
+        if self.fp8:
+            self.scales = scales if scales is not None else [
+                torch.ones(4, nkv, dtype=torch.float32, device=device)
+                for _ in range(cfg.n_layers)]
+            if len(self.scales) != cfg.n_layers or any(
+                    tuple(t.shape) != (4, nkv) or t.dtype != torch.float32
+                    for t in self.scales):
+                raise ValueError(f"fp8 scales must be {cfg.n_layers} float32 "
+                                 f"[4, {nkv}] tensors")
+
+    def set_scales(self, k_scales, v_scales) -> None:
+        """Per-layer [Hkv] k / v scales, written in place."""
+        if not self.fp8:
+            raise ValueError("only an fp8 KVCache has scales")
+        write_kv_scales(self.scales, k_scales, v_scales)
+
+
+def write_kv_scales(scales: list, k_scales, v_scales) -> None:
+    """Write per-layer [Hkv] k / v scales and their reciprocals
+    (torch.reciprocal: the kernels only multiply) IN PLACE into the
+    [4, Hkv] tensors `scales`.  Validates everything before the first
+    write."""
+    if len(k_scales) != len(scales) or len(v_scales) != len(scales):
+        raise ValueError(f"need {len(scales)} per-layer scale rows")
+    rows = []
+    for sc, ks, vs in zip(scales, k_scales, v_scales):
+        k1 = torch.as_tensor(ks, dtype=torch.float32).reshape(-1).cpu()
+        v1 = torch.as_tensor(vs, dtype=torch.float32).reshape(-1).cpu()
+        if k1.numel() != sc.shape[1] or v1.numel() != sc.shape[1]:
+            raise ValueError(f"scales must be [{sc.shape[1]}] per layer")
+        kv = torch.stack([k1, v1])
+        if not bool(torch.isfinite(kv).all()) or not bool((kv > 0).all()):
+            raise ValueError("kv scales must be finite and positive")
+        rows.append(kv)
+    for sc, kv in zip(scales, rows):
+        kv = kv.to(sc.device)
+        sc[:2].copy_(kv)
+        sc[2:].copy_(torch.reciprocal(kv))
 
 
 class Transformer:
@@ -180,6 +256,10 @@ class Transformer:
         q = ops.rope_apply(q, self.rope_cos, self.rope_sin, pos)
         k = ops.rope_apply(k, self.rope_cos, self.rope_sin, pos)
 
+        if cache is not None and cache.fp8:
+            raise ValueError("prefill writes exact K/V: run it into a bf16 "
+                             "staging KVCache and splice with "
+                             "ops.kv_store_fp8")
         if cache is not None:
             # write k/v at pos into the cache: [B, Hkv_local, Smax, hd]
             kc, vc = cache.k[layer_idx], cache.v[layer_idx]
@@ -272,7 +352,14 @@ class Transformer:
         d = self.cfg.dim
         hd = self.cfg.head_dim
         qkv = ops.lt_linear(normed.view(B, d), layer["wqkv"])
-        if self._decode_fused(qkv):
+        if cache.fp8:
+            # FP8 cache: one launch as below, quantising the new row
+            sc = cache.scales[layer_idx]
+            out = ops.decode_attention_fused_fp8(
+                qkv, cache.k[layer_idx], cache.v[layer_idx], self.rope_cos,
+                self.rope_sin, cache.seq_lens, sc[0], sc[1], sc[2], sc[3],
+                self.scale)
+        elif self._decode_fused(qkv):
             # one launch: RoPE(q) in registers, KV row written and attended
             out = ops.decode_attention_fused(
                 qkv, cache.k[layer_idx], cache.v[layer_idx], self.rope_cos,

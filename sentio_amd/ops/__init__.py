@@ -178,6 +178,114 @@ def decode_attention_fused(qkv, k_cache, v_cache, cos, sin, seq_lens,
                                             seq_lens, s)
 
 
+def _check_fp8_caches(k_cache, v_cache):
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("fp8 caches must be two [B,Hkv,Smax,D] tensors of "
+                         "equal shape")
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8:
+        raise ValueError("fp8 caches must be uint8 (e4m3fn bytes), got "
+                         f"{k_cache.dtype} / {v_cache.dtype}")
+
+
+def _check_kv_scales(k_cache, **scales):
+    Hkv = k_cache.shape[1]
+    for name, t in scales.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 \
+                or tuple(t.shape) != (Hkv,) or not t.is_contiguous() \
+                or t.device != k_cache.device:
+            raise ValueError(f"{name}: kv scale must be a contiguous float32 "
+                             f"[{Hkv}] tensor on {k_cache.device}")
+
+
+def decode_attention_fused_fp8(qkv, k_cache, v_cache, cos, sin, seq_lens,
+                               k_scale, v_scale, k_inv=None, v_inv=None,
+                               scale: float | None = None):
+    """ops.decode_attention_fused over an FP8 (e4m3fn) KV cache: uint8
+    caches [B, Hkv, Smax, D] with static fp32 [Hkv] scales.  The new k row
+    is rotated and rounded as the bf16 op stores it, then quantised
+    (torch_ref.kv_quantize is the spec) and written with the v row at
+    seq_lens[b]; attention covers the dequantised seq_lens[b] + 1 keys, the
+    new token included as stored.  k_inv / v_inv are the reciprocals of the
+    scales (torch.reciprocal, computed here when not given — hold them next
+    to the scales on a hot path).  Returns [B, H, D]."""
+    if qkv.dim() != 2:
+        raise ValueError("qkv must be [B, (H+2*Hkv)*D]")
+    _check_fp8_caches(k_cache, v_cache)
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    if D not in (64, 128):
+        raise ValueError(f"head dim must be 64 or 128, got {D}")
+    H = qkv.shape[1] // D - 2 * Hkv
+    if H <= 0 or H % Hkv or (H + 2 * Hkv) * D != qkv.shape[1]:
+        raise ValueError(
+            f"qkv width {qkv.shape[1]} is not (H+2*{Hkv})*{D} for a whole "
+            "number of query heads per kv head")
+    if H // Hkv > 8:
+        raise ValueError(f"at most 8 query heads per kv head, got {H // Hkv}")
+    if seq_lens.dtype != torch.int32 or not seq_lens.is_contiguous() \
+            or seq_lens.numel() != qkv.shape[0]:
+        raise ValueError("seq_lens must be a contiguous int32 [B] tensor")
+    if k_inv is None:
+        k_inv = torch.reciprocal(k_scale)
+    if v_inv is None:
+        v_inv = torch.reciprocal(v_scale)
+    _check_kv_scales(k_cache, k_scale=k_scale, v_scale=v_scale, k_inv=k_inv,
+                     v_inv=v_inv)
+    s = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    if _on_gpu(qkv):
+        return _require_hip().decode_attn_fused_fp8(
+            qkv.contiguous(), k_cache, v_cache, cos, sin, seq_lens, k_scale,
+            v_scale, k_inv, v_inv, s)
+    return torch_ref.decode_attention_fused_fp8(
+        qkv, k_cache, v_cache, cos, sin, seq_lens, k_scale, v_scale, k_inv,
+        v_inv, s)
+
+
+def kv_store_fp8(src_k, src_v, k_cache, v_cache, rows, S: int, k_inv, v_inv):
+    """Quantising splice into an FP8 KV cache: the first S rows of the bf16
+    sources [n, Hkv, S_src, D] are quantised (torch_ref.kv_quantize) into
+    cache[rows[i], :, :S]; K and V in one launch.  rows: a Python sequence
+    (checked here for range and duplicates) or an int tensor on the caches'
+    device (the kernel skips entries outside [0, B)).  k_inv / v_inv:
+    reciprocal scales, fp32 [Hkv]."""
+    _check_fp8_caches(k_cache, v_cache)
+    if src_k.dim() != 4 or src_v.shape != src_k.shape:
+        raise ValueError("sources must be two [n,Hkv,S_src,D] tensors of "
+                         "equal shape")
+    B, Hkv, Smax, D = k_cache.shape
+    n, _, S_src, _ = src_k.shape
+    if src_k.shape[1] != Hkv or src_k.shape[3] != D:
+        raise ValueError("source and cache kv heads / head dim differ")
+    if D % 8:
+        raise ValueError(f"head dim must be a multiple of 8, got {D}")
+    S = int(S)
+    if S < 0 or S > min(S_src, Smax):
+        raise ValueError(f"S={S} exceeds min(S_src={S_src}, Smax={Smax})")
+    _check_kv_scales(k_cache, k_inv=k_inv, v_inv=v_inv)
+    if isinstance(rows, torch.Tensor):
+        if rows.dim() != 1 or rows.numel() != n or rows.dtype not in (
+                torch.int32, torch.int64) or rows.device != k_cache.device:
+            raise ValueError("rows must be an int32/int64 [n] tensor on the "
+                             "caches' device")
+        rows_t = rows.to(torch.int32).contiguous()
+    else:
+        rows = [int(r) for r in rows]
+        if len(rows) != n:
+            raise ValueError(f"{len(rows)} rows for {n} sources")
+        if any(r < 0 or r >= B for r in rows):
+            raise ValueError(f"rows {rows} outside [0, {B})")
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"duplicate rows in {rows}")
+        rows_t = torch.tensor(rows, dtype=torch.int32, device=k_cache.device)
+    if _on_gpu(k_cache):
+        if src_k.dtype != torch.bfloat16 or src_v.dtype != torch.bfloat16:
+            raise ValueError("sources must be bf16 on the GPU")
+        _require_hip().kv_store_fp8(src_k.contiguous(), src_v.contiguous(),
+                                    k_cache, v_cache, rows_t, S, k_inv, v_inv)
+        return
+    torch_ref.kv_store_fp8(src_k, src_v, k_cache, v_cache, rows_t, S, k_inv,
+                           v_inv)
+
+
 def decode_attention_bmm(q, k_cache, v_cache, seq_lens,
                          scale: float | None = None):
     """Decode attention as two rocBLAS batched GEMMs over the FULL cache
@@ -385,7 +493,7 @@ def gemm_bf16(a, b):
 
 
 __all__ = [
-    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "swiglu", "swiglu_packed", "softmax",
+    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -11,6 +11,9 @@
 //    wave-private online softmax (no LDS or barrier in the key loop); a
 //    combine kernel reduces the splits when there is more than one.  The
 //    fused variant also applies RoPE and appends the new token's k/v row.
+//  * decode_attn_fp8 / kv_store_fp8 — the opt-in FP8 (e4m3fn) KV cache: the
+//    fused decode kernel over uint8 caches with static per-kv-head scales,
+//    and the quantising splice of bf16 prefill K/V into such a cache.
 //
 // Replaces (K6 prefill/decode in SURVEY §2.3) the reference's remote
 // /chat/completions calls (reference src/core/llm/providers/openai.py:117).
@@ -653,6 +656,422 @@ __global__ void decode_attn_kernel(
   }
 }
 
+// ------------------------------------------------------------ FP8 KV cache
+// Opt-in e4m3fn (OCP, = torch.float8_e4m3fn) cache: uint8 [B, Hkv, Smax, D]
+// with static fp32 scales per kv head.  Quantisation is
+//   byte = RNE_e4m3fn(clamp(fp32(x) * inv, -448, +448))
+// with the clamp done in fp32 ahead of v_cvt_pk_fp8_f32 (no reliance on a
+// saturation mode bit), so a finite input never yields 0x7F / 0xFF.  The
+// kernels only multiply: inv = 1/scale is computed once on the host side.
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#define FP8_E4M3_MAX 448.f
+
+__device__ __forceinline__ float fp8_clamp(float x) {
+  return __builtin_fminf(__builtin_fmaxf(x, -FP8_E4M3_MAX), FP8_E4M3_MAX);
+}
+// 8 bf16 (raw bits) * inv -> 8 e4m3fn bytes, element e in byte e
+__device__ __forceinline__ u32x2_t fp8_quant8(bf16x8 x, float inv) {
+  float f[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = fp8_clamp(bits2f(x[e]) * inv);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  u32x2_t r;
+  r.x = (unsigned)lo;
+  r.y = (unsigned)hi;
+  return r;
+}
+// 8 e4m3fn bytes -> 8 floats (unscaled): four v_cvt_pk_f32_fp8
+__device__ __forceinline__ void fp8_unpack8(u32x2_t w, float (&f)[8]) {
+  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false);
+  const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false);
+  const f32x2_t d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+  f[0] = a.x; f[1] = a.y; f[2] = b.x; f[3] = b.y;
+  f[4] = c.x; f[5] = c.y; f[6] = d.x; f[7] = d.y;
+}
+
+// 8 or 16 e4m3fn bytes per lane and key: one 8 B / 16 B non-temporal load
+template <int EPL> struct Fp8Row;
+template <> struct Fp8Row<8> {
+  u32x2_t w;
+  __device__ __forceinline__ void load(const unsigned char* p) {
+    w = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
+  }
+  __device__ __forceinline__ void store(unsigned char* p) const {
+    *reinterpret_cast<u32x2_t*>(p) = w;
+  }
+  __device__ __forceinline__ u32x2_t chunk(int) const { return w; }
+  __device__ __forceinline__ void set(int, u32x2_t v) { w = v; }
+};
+template <> struct Fp8Row<16> {
+  u32x4_t w;
+  __device__ __forceinline__ void load(const unsigned char* p) {
+    w = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+  }
+  __device__ __forceinline__ void store(unsigned char* p) const {
+    *reinterpret_cast<u32x4_t*>(p) = w;
+  }
+  __device__ __forceinline__ u32x2_t chunk(int c) const {
+    u32x2_t r;
+    r.x = c ? w.z : w.x;
+    r.y = c ? w.w : w.y;
+    return r;
+  }
+  __device__ __forceinline__ void set(int c, u32x2_t v) {
+    if (c) { w.z = v.x; w.w = v.y; } else { w.x = v.x; w.y = v.y; }
+  }
+};
+template <int EPL>
+__device__ __forceinline__ void fp8_unpack_row(const Fp8Row<EPL>& r,
+                                               float (&f)[EPL]) {
+#pragma unroll
+  for (int c = 0; c < EPL / 8; ++c) {
+    float t[8];
+    fp8_unpack8(r.chunk(c), t);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[c * 8 + e] = t[e];
+  }
+}
+// sum over the LPK (16 or 8) lanes of a key, result in every lane
+template <int LPK>
+__device__ __forceinline__ float key_sum_dpp(float v) {
+  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);   // row_half_mirror
+  if (LPK == 16) v += dpp_mov<0x140>(v);   // row_mirror
+  return v;
+}
+
+// Elements per lane of the FP8 kernel.  8: the (li, g4) mapping of the bf16
+// kernel, 16 lanes and an 8 B load per key, 4 keys per wave instruction.
+// 16 (D = 128, G <= 4): 8 lanes and a 16 B load per key, 8 keys per wave
+// instruction, an 8-lane DPP sum — half the reduction work per key, but q
+// and o take 32 registers per query head, which fits without scratch only
+// up to G = 4.  Measured, llama3-8b heads (profiles/kv_fp8.md): 16 is 9-12%
+// faster at 1600 keys and 8% slower at 512; both beat the bf16 kernel.
+template <int G, int DT> struct Fp8Epl {
+  static constexpr int value = (DT == 128 && G <= 4) ? 16 : 8;
+};
+
+// FP8 sibling of decode_attn_kernel<FUSED> (the bf16 instantiations are not
+// touched): same grid, split, wave and seq_lens contract.  A key's row is
+// covered by LPK lanes of EPL dims each; a lane loads EPL bytes of K and of
+// V per key and unpacks them with v_cvt_pk_f32_fp8.  A batch is two halves
+// of SUB keys per lane group (one at G = 8): all loads of both halves issue
+// back to back, in the order they are consumed, then the softmax update
+// runs per half, so the score registers stay those of the bf16 kernel (one
+// update over the whole batch spilled to scratch at G >= 4).  At EPL = 8 a
+// batch holds the bf16 kernel's load registers and bytes in flight.
+//   * the new k row is rotated and rounded to bf16 exactly as the bf16
+//     fused kernel stores it, then quantised; the bytes stored are
+//     quantise(that row).  v likewise.
+//   * the new token enters its own attention as the DEQUANTISED stored
+//     value: this step sees the K/V every later step will read.
+//   * k_scale folds into the pre-scaled q registers; v_scale multiplies the
+//     reduced numerator, both at splits == 1 and in the ws_o partials, so
+//     decode_attn_combine_kernel and the ws_ml contract are unchanged.
+// scales are read at run time (in-place updates need no graph recapture).
+template <int G, int DT, int NW, int EPL>
+__launch_bounds__(NW * WAVE)
+__global__ void decode_attn_fp8_kernel(
+    const bf16* __restrict__ qsrc, unsigned char* kc, unsigned char* vc,
+    float* __restrict__ ws_o, float* __restrict__ ws_ml,
+    bf16* __restrict__ out,
+    const float* __restrict__ cosT, const float* __restrict__ sinT,
+    const int* __restrict__ seq_lens,
+    const float* __restrict__ k_scale, const float* __restrict__ v_scale,
+    const float* __restrict__ k_inv, const float* __restrict__ v_inv,
+    int H, int Hkv, int Smax, float scale, int splits) {
+  constexpr int D = DT;
+  constexpr int ROWB = D / EPL;            // lanes that cover one K row
+  constexpr int LPK = EPL == 16 ? 8 : 16;  // lanes per key (>= ROWB)
+  constexpr int KPW = WAVE / LPK;          // keys per wave instruction
+  constexpr int NC = EPL / 8;              // 8-element chunks per lane
+  static_assert(ROWB <= LPK, "row wider than its lane group");
+  // EPL = 16 halves the sub-batch: its q, o and load registers are twice as
+  // wide.  G = 8 keeps one half: q and o alone hold 128 registers there.
+  constexpr int SUB = EPL == 16 ? 2 : DecBatch<G>::value;
+  constexpr int HALVES = G <= 7 ? 2 : 1;
+  constexpr int KB = HALVES * SUB;         // keys per lane group per batch
+  constexpr float LOG2E = 1.4426950408889634f;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sm_o = reinterpret_cast<float*>(smem);            // [NW][G][D]
+  float* sm_ml = sm_o + NW * G * D;                        // [NW][G][2]
+
+  const int hkv = blockIdx.x;
+  const int b = blockIdx.y;
+  const int split = blockIdx.z;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int li = lane & (LPK - 1);         // lane-in-group: dim slice owner
+  const int gk = lane / LPK;               // group in wave: key owner
+  const int ls = li % ROWB;                // D=64: upper lanes duplicate
+  const int len_raw = seq_lens[b];
+  const int slen = max(0, min(len_raw, Smax));   // cache rows to stream
+  const int span = (slen + splits - 1) / splits;
+  const int s_begin = split * span;
+  const int s_end = min(slen, s_begin + span);
+  const long cache_off = ((long)b * Hkv + hkv) * Smax * (long)D;
+  // block-uniform bases + one 32-bit lane offset shared by the K and V
+  // load of a key (a (b, kv-head) slab is far below 4 GB): scalar base +
+  // 1-VGPR offset addressing instead of a 64-bit address pair per load
+  const unsigned char* kb = kc + cache_off;
+  const unsigned char* vb = vc + cache_off;
+  const int lo = ls * EPL;
+
+  // ---- q slice: RoPE, bf16 rounding, pre-scaled by scale*log2e*k_scale
+  const int HT = H + 2 * Hkv;
+  const int pos = max(0, min(len_raw, Smax - 1));
+  const long toff = (long)pos * (D / 2) + ls * (EPL / 2);
+  float4 rc[NC], rs[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    rc[c] = *reinterpret_cast<const float4*>(cosT + toff + c * 4);
+    rs[c] = *reinterpret_cast<const float4*>(sinT + toff + c * 4);
+  }
+  const float qs = scale * LOG2E * k_scale[hkv];
+  float q_reg[G][EPL];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const bf16* qp = qsrc + ((long)b * HT + hkv * G + g) * D + lo;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const bf16x8 qv = rope_slice(
+          *reinterpret_cast<const bf16x8*>(qp + c * 8), rc[c], rs[c]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) q_reg[g][c * 8 + e] = bits2f(qv[e]) * qs;
+    }
+  }
+
+  float m_run[G], l_run[G], o[G][EPL];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    m_run[g] = -INFINITY;
+    l_run[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) o[g][e] = 0.f;
+  }
+
+  // ---- the new token, owned by the last split's block
+  if (split == splits - 1) {
+    const bf16* krow = qsrc + ((long)b * HT + H + hkv) * D + lo;
+    const float ki = k_inv[hkv], vi = v_inv[hkv];
+    Fp8Row<EPL> kq, vq;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const bf16x8 kn = rope_slice(
+          *reinterpret_cast<const bf16x8*>(krow + c * 8), rc[c], rs[c]);
+      const bf16x8 vn =
+          *reinterpret_cast<const bf16x8*>(krow + (long)Hkv * D + c * 8);
+      kq.set(c, fp8_quant8(kn, ki));
+      vq.set(c, fp8_quant8(vn, vi));
+    }
+    const bool take = wid == 0 && gk == 0;
+    if (take && li < ROWB && len_raw >= 0 && len_raw < Smax) {
+      const long row = cache_off + (long)len_raw * D + li * EPL;
+      kq.store(kc + row);
+      vq.store(vc + row);
+    }
+    float kf[EPL], vf[EPL];
+    fp8_unpack_row<EPL>(kq, kf);
+    fp8_unpack_row<EPL>(vq, vf);
+    float sn[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float acc = 0.f;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc += kf[e] * q_reg[g][e];
+      if (ROWB < LPK) acc = (li < ROWB) ? acc : 0.f;
+      sn[g] = key_sum_dpp<LPK>(acc);
+    }
+    if (take) {                            // p = exp2(s - s) = 1
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        m_run[g] = sn[g];
+        l_run[g] = 1.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) o[g][e] = vf[e];
+      }
+    }
+  }
+
+  // ---- key loop: wave-private, no LDS, no barrier
+  const int nbatch = (s_end - s_begin + KPW * KB - 1) / (KPW * KB);
+  for (int t = wid; t < nbatch; t += NW) {
+    const int k0 = s_begin + t * (KPW * KB) + gk;
+    // issue order = consume order (K h0, V h0, K h1, V h1): the in-order
+    // vmcnt waits then never drain loads that are not needed yet
+    Fp8Row<EPL> kr[HALVES][SUB], vr[HALVES][SUB];
+#pragma unroll
+    for (int h = 0; h < HALVES; ++h) {
+#pragma unroll
+      for (int u = 0; u < SUB; ++u)
+        kr[h][u].load(kb + (unsigned)(
+            min(k0 + (h * SUB + u) * KPW, s_end - 1) * D + lo));
+#pragma unroll
+      for (int u = 0; u < SUB; ++u)
+        vr[h][u].load(vb + (unsigned)(
+            min(k0 + (h * SUB + u) * KPW, s_end - 1) * D + lo));
+    }
+    // all 2*KB loads ahead of the first use (see decode_attn_kernel)
+    __builtin_amdgcn_sched_barrier(0);
+
+#pragma unroll
+    for (int h = 0; h < HALVES; ++h) {
+      float s[SUB][G];
+#pragma unroll
+      for (int u = 0; u < SUB; ++u) {
+        float kf[EPL];
+        fp8_unpack_row<EPL>(kr[h][u], kf);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          float acc = 0.f;
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) acc += kf[e] * q_reg[g][e];
+          if (ROWB < LPK) acc = (li < ROWB) ? acc : 0.f;
+          acc = key_sum_dpp<LPK>(acc);
+          s[u][g] = (k0 + (h * SUB + u) * KPW < s_end) ? acc : -INFINITY;
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float mx = s[0][g];
+#pragma unroll
+        for (int u = 1; u < SUB; ++u) mx = fmaxf(mx, s[u][g]);
+        const float m_new = fmaxf(m_run[g], mx);
+        const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
+        const float alpha = fast_exp2(m_run[g] - m_safe);
+        m_run[g] = m_new;
+        float l = l_run[g] * alpha;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) o[g][e] *= alpha;
+#pragma unroll
+        for (int u = 0; u < SUB; ++u) {
+          const float p = fast_exp2(s[u][g] - m_safe);
+          s[u][g] = p;
+          l += p;
+        }
+        l_run[g] = l;
+      }
+#pragma unroll
+      for (int u = 0; u < SUB; ++u) {
+        float vf[EPL];
+        fp8_unpack_row<EPL>(vr[h][u], vf);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) o[g][e] += s[u][g] * vf[e];
+      }
+      // the halves stay apart: interleaved, their unpacked floats and
+      // scores are live together and the kernel spills
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // ---- fold the wave's lane groups (same dim slice, different keys)
+#pragma unroll
+  for (int off = LPK; off <= 32; off <<= 1) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float mo = __shfl_xor(m_run[g], off, WAVE);
+      const float lo_ = __shfl_xor(l_run[g], off, WAVE);
+      const float mm = fmaxf(m_run[g], mo);
+      const float ms = (mm == -INFINITY) ? 0.f : mm;
+      const float a = fast_exp2(m_run[g] - ms);
+      const float ao = fast_exp2(mo - ms);
+      l_run[g] = l_run[g] * a + lo_ * ao;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e)
+        o[g][e] = o[g][e] * a + __shfl_xor(o[g][e], off, WAVE) * ao;
+      m_run[g] = mm;
+    }
+  }
+
+  // ---- fold the waves through LDS, one barrier
+  if (gk == 0 && li < ROWB) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float4* dst =
+          reinterpret_cast<float4*>(sm_o + (wid * G + g) * D + li * EPL);
+#pragma unroll
+      for (int j = 0; j < EPL / 4; ++j)
+        dst[j] = make_float4(o[g][4 * j], o[g][4 * j + 1], o[g][4 * j + 2],
+                             o[g][4 * j + 3]);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      sm_ml[(wid * G + g) * 2 + 0] = m_run[g];
+      sm_ml[(wid * G + g) * 2 + 1] = l_run[g];
+    }
+  }
+  __syncthreads();
+
+  const float vs = v_scale[hkv];
+  const long base = (((long)b * Hkv + hkv) * splits + split) * G;
+  for (int i = threadIdx.x; i < G * D; i += NW * WAVE) {
+    const int g = i / D, d = i % D;
+    float M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_ml[(w * G + g) * 2]);
+    const float ms = (M == -INFINITY) ? 0.f : M;
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const float a = fast_exp2(sm_ml[(w * G + g) * 2] - ms);
+      den += sm_ml[(w * G + g) * 2 + 1] * a;
+      num += sm_o[(w * G + g) * D + d] * a;
+    }
+    num *= vs;
+    if (splits == 1) {
+      out[((long)b * H + hkv * G + g) * D + d] =
+          f2bf(den > 0.f ? num / den : 0.f);
+    } else {
+      ws_o[(base + g) * D + d] = num;
+      if (d == 0) {                        // m back in natural-log units
+        ws_ml[(base + g) * 2 + 0] = M * (1.f / LOG2E);
+        ws_ml[(base + g) * 2 + 1] = den;
+      }
+    }
+  }
+}
+
+// Quantising splice: the first S rows of each bf16 source row
+// [n, Hkv, S_src, D] go to dst[rows[i], :, :S, :] of the uint8 caches
+// [B, Hkv, Smax, D]; K and V in one launch.  One thread per 8 elements:
+// a 16 B load and an 8 B store per tensor.  rows[i] outside [0, B) is
+// skipped; nothing is written beyond S or Smax.
+__global__ void kv_store_fp8_kernel(
+    const bf16* __restrict__ src_k, const bf16* __restrict__ src_v,
+    unsigned char* __restrict__ dst_k, unsigned char* __restrict__ dst_v,
+    const int* __restrict__ rows, const float* __restrict__ k_inv,
+    const float* __restrict__ v_inv, long total, int B, int Hkv, int S_src,
+    int S, int Smax, int D) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int d8n = D / 8;
+  const int d8 = (int)(i % d8n);
+  long t = i / d8n;
+  const int s = (int)(t % S);
+  t /= S;
+  const int h = (int)(t % Hkv);
+  const long r = t / Hkv;
+  const int row = rows[r];
+  if (row < 0 || row >= B || s >= Smax || s >= S_src) return;
+  const long so = ((r * Hkv + h) * S_src + s) * (long)D + d8 * 8;
+  const long dof = (((long)row * Hkv + h) * Smax + s) * (long)D + d8 * 8;
+  const bf16x8 kv = *reinterpret_cast<const bf16x8*>(src_k + so);
+  const bf16x8 vv = *reinterpret_cast<const bf16x8*>(src_v + so);
+  *reinterpret_cast<u32x2_t*>(dst_k + dof) = fp8_quant8(kv, k_inv[h]);
+  *reinterpret_cast<u32x2_t*>(dst_v + dof) = fp8_quant8(vv, v_inv[h]);
+}
+
 // combine: one block per (b, h); threads over D
 __global__ void decode_attn_combine_kernel(
     const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
@@ -734,6 +1153,57 @@ static hipError_t launch_decode_attn(const void* qsrc, void* kc, void* vc,
   return hipSuccess;
 }
 
+// FP8-cache launcher: the checks, grid, LDS size and combine step of
+// launch_decode_attn<true>.
+static hipError_t launch_decode_attn_fp8(
+    const void* qsrc, void* kc, void* vc, void* out, const float* cosT,
+    const float* sinT, const int* seq_lens, const float* k_scale,
+    const float* v_scale, const float* k_inv, const float* v_inv, float* ws_o,
+    float* ws_ml, int splits, int waves, int B, int H, int Hkv, int Smax,
+    int D, float scale, hipStream_t stream) {
+  if (Hkv < 1 || H < 1 || H % Hkv || Smax < 1 || B < 1 || splits < 1 ||
+      (D != 64 && D != 128) || (waves != 4 && waves != 8))
+    return hipErrorInvalidValue;
+  if (!k_scale || !v_scale || !k_inv || !v_inv) return hipErrorInvalidValue;
+  // the kernel addresses a (b, kv-head) slab with 32-bit byte offsets
+  if ((long)Smax * D > 0x7fffffffL) return hipErrorInvalidValue;
+  const int G = H / Hkv;
+  if (G > DEC_MAXG) return hipErrorInvalidValue;
+  if (splits > 1 && (!ws_o || !ws_ml)) return hipErrorInvalidValue;
+  const size_t lds = (size_t)waves * (G * D + 2 * G) * sizeof(float);
+  dim3 grid(Hkv, B, splits);
+#define DEC8_LAUNCH(GV, DV, NWV)                                              \
+  hipLaunchKernelGGL(                                                         \
+      (decode_attn_fp8_kernel<GV, DV, NWV, Fp8Epl<GV, DV>::value>), grid,     \
+                     dim3(NWV * WAVE), lds, stream, (const bf16*)qsrc,        \
+                     (unsigned char*)kc, (unsigned char*)vc, ws_o, ws_ml,     \
+                     (bf16*)out, cosT, sinT, seq_lens, k_scale, v_scale,      \
+                     k_inv, v_inv, H, Hkv, Smax, scale, splits)
+#define DEC8_CASE(GV, DV)                                                     \
+  case GV * 1000 + DV:                                                        \
+    if (waves == 8) DEC8_LAUNCH(GV, DV, 8);                                   \
+    else DEC8_LAUNCH(GV, DV, 4);                                              \
+    break;
+#define DEC8_ALL_G(DV)                                                    \
+  DEC8_CASE(1, DV) DEC8_CASE(2, DV) DEC8_CASE(3, DV) DEC8_CASE(4, DV)     \
+  DEC8_CASE(5, DV) DEC8_CASE(6, DV) DEC8_CASE(7, DV) DEC8_CASE(8, DV)
+  switch (G * 1000 + D) {
+    DEC8_ALL_G(64) DEC8_ALL_G(128)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef DEC8_ALL_G
+#undef DEC8_CASE
+#undef DEC8_LAUNCH
+  HIP_CHECK_LAUNCH();
+  if (splits > 1) {
+    hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(H, B), dim3(128), 0,
+                       stream, ws_o, ws_ml, (bf16*)out, H, G, D, splits);
+    HIP_CHECK_LAUNCH();
+  }
+  return hipSuccess;
+}
+
 // One launcher for both prefill entry points: CACHE_SRC picks the K/V
 // layout, plain prefill passes Smax = q_off = 0.
 template <bool CACHE_SRC>
@@ -804,6 +1274,40 @@ hipError_t sentio_decode_attn_fused(const void* qkv, void* kc, void* vc,
   return launch_decode_attn<true>(qkv, kc, vc, out, cosT, sinT, seq_lens,
                                   ws_o, ws_ml, splits, waves, B, H, Hkv, Smax,
                                   D, scale, stream);
+}
+
+hipError_t sentio_decode_attn_fused_fp8(
+    const void* qkv, void* kc, void* vc, void* out, const float* cosT,
+    const float* sinT, const int* seq_lens, const float* k_scale,
+    const float* v_scale, const float* k_inv, const float* v_inv, float* ws_o,
+    float* ws_ml, int splits, int waves, int B, int H, int Hkv, int Smax,
+    int D, float scale, hipStream_t stream) {
+  return launch_decode_attn_fp8(qkv, kc, vc, out, cosT, sinT, seq_lens,
+                                k_scale, v_scale, k_inv, v_inv, ws_o, ws_ml,
+                                splits, waves, B, H, Hkv, Smax, D, scale,
+                                stream);
+}
+
+hipError_t sentio_kv_store_fp8(const void* src_k, const void* src_v,
+                               void* dst_k, void* dst_v, const int* rows,
+                               const float* k_inv, const float* v_inv, int n,
+                               int B, int Hkv, int S_src, int S, int Smax,
+                               int D, hipStream_t stream) {
+  if (n < 0 || B < 1 || Hkv < 1 || S < 0 || S > S_src || S > Smax ||
+      D < 8 || (D % 8) || !rows || !k_inv || !v_inv)
+    return hipErrorInvalidValue;
+  const long total = (long)n * Hkv * S * (D / 8);
+  if (total == 0) return hipSuccess;
+  const int threads = 256;
+  const long blocks = (total + threads - 1) / threads;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kv_store_fp8_kernel, dim3((unsigned)blocks),
+                     dim3(threads), 0, stream, (const bf16*)src_k,
+                     (const bf16*)src_v, (unsigned char*)dst_k,
+                     (unsigned char*)dst_v, rows, k_inv, v_inv, total, B, Hkv,
+                     S_src, S, Smax, D);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
 }
 
 }  // extern "C"

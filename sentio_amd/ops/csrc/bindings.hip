@@ -369,6 +369,107 @@ torch::Tensor decode_attn_fused(torch::Tensor qkv, torch::Tensor kc,
   return out;
 }
 
+// ---- FP8 (e4m3fn) KV cache: uint8 caches + fp32 [Hkv] scales
+void check_caches_u8(const torch::Tensor& kc, const torch::Tensor& vc) {
+  for (const auto* t : {&kc, &vc}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kByte &&
+                t->is_contiguous(),
+                "fp8 caches must be contiguous uint8 GPU tensors");
+  }
+  TORCH_CHECK(kc.dim() == 4, "k cache must be [B,Hkv,Smax,D]");
+  TORCH_CHECK(vc.sizes() == kc.sizes(), "k and v cache shapes differ");
+}
+
+void check_kv_scale(const torch::Tensor& t, const torch::Tensor& like,
+                    long Hkv, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
+              t.scalar_type() == torch::kFloat && t.is_contiguous() &&
+              t.dim() == 1 && t.size(0) == Hkv,
+              name, ": kv scale must be a contiguous f32 [Hkv] tensor on the "
+              "caches' device");
+}
+
+// decode_attn_fused over an FP8 cache: the new k/v row is quantised with
+// k_inv/v_inv and attended as its dequantised stored value.
+torch::Tensor decode_attn_fused_fp8(torch::Tensor qkv, torch::Tensor kc,
+                                    torch::Tensor vc, torch::Tensor cosT,
+                                    torch::Tensor sinT, torch::Tensor seq_lens,
+                                    torch::Tensor k_scale,
+                                    torch::Tensor v_scale, torch::Tensor k_inv,
+                                    torch::Tensor v_inv, double scale) {
+  check_bf16_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (H+2*Hkv)*D]");
+  check_caches_u8(kc, vc);
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == torch::kInt &&
+              seq_lens.is_contiguous(),
+              "seq_lens must be a contiguous i32 GPU tensor");
+  const int B = qkv.size(0);
+  const int Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
+  const int H = (int)(qkv.size(1) / D) - 2 * Hkv;
+  TORCH_CHECK(H > 0 && H % Hkv == 0 &&
+              (long)(H + 2 * Hkv) * D == qkv.size(1), "qkv width mismatch");
+  TORCH_CHECK(H / Hkv <= 8, "at most 8 query heads per kv head, got ",
+              H / Hkv);
+  TORCH_CHECK(kc.size(0) >= B && seq_lens.numel() == B,
+              "batch mismatch between qkv, caches and seq_lens");
+  for (const auto* t : {&cosT, &sinT}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                t->is_contiguous() && t->dim() == 2 && t->size(0) >= Smax &&
+                t->size(1) == D / 2,
+                "rope tables must be contiguous f32 [>=Smax, D/2] on GPU");
+  }
+  check_kv_scale(k_scale, kc, Hkv, "k_scale");
+  check_kv_scale(v_scale, kc, Hkv, "v_scale");
+  check_kv_scale(k_inv, kc, Hkv, "k_inv");
+  check_kv_scale(v_inv, kc, Hkv, "v_inv");
+  auto out = torch::empty({B, H, D}, qkv.options());
+  const auto [splits, waves] = decode_attn_plan(B, Hkv, Smax);
+  DecodeWorkspace ws(qkv, splits, B, Hkv, H / Hkv, D);
+  check_hip(sentio_decode_attn_fused_fp8(
+                qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                cosT.data_ptr<float>(), sinT.data_ptr<float>(),
+                seq_lens.data_ptr<int>(), k_scale.data_ptr<float>(),
+                v_scale.data_ptr<float>(), k_inv.data_ptr<float>(),
+                v_inv.data_ptr<float>(), ws.o_ptr, ws.ml_ptr, splits, waves,
+                B, H, Hkv, Smax, D, (float)scale, stream()),
+            "decode_attn_fused_fp8");
+  return out;
+}
+
+// Quantising splice of bf16 staging K/V [n,Hkv,S_src,D] into rows[i] of the
+// uint8 caches, first S sequence rows.
+void kv_store_fp8(torch::Tensor src_k, torch::Tensor src_v, torch::Tensor kc,
+                  torch::Tensor vc, torch::Tensor rows, long S,
+                  torch::Tensor k_inv, torch::Tensor v_inv) {
+  check_bf16_cuda(src_k, "src_k");
+  check_bf16_cuda(src_v, "src_v");
+  TORCH_CHECK(src_k.dim() == 4 && src_v.sizes() == src_k.sizes(),
+              "sources must be two [n,Hkv,S_src,D] tensors of equal shape");
+  check_caches_u8(kc, vc);
+  const long n = src_k.size(0), Hkv = kc.size(1), Smax = kc.size(2);
+  const long D = kc.size(3), S_src = src_k.size(2);
+  TORCH_CHECK(src_k.size(1) == Hkv && src_k.size(3) == D,
+              "source and cache kv heads / head dim differ");
+  TORCH_CHECK(D % 8 == 0, "head dim must be a multiple of 8, got ", D);
+  TORCH_CHECK(S >= 0 && S <= S_src && S <= Smax,
+              "S must be <= min(S_src, Smax), got ", S);
+  TORCH_CHECK(rows.is_cuda() && rows.device() == kc.device() &&
+              rows.scalar_type() == torch::kInt && rows.is_contiguous() &&
+              rows.dim() == 1 && rows.numel() == n,
+              "rows must be a contiguous i32 [n] tensor on the caches' device");
+  TORCH_CHECK(src_k.device() == kc.device(), "sources and caches on "
+              "different devices");
+  check_kv_scale(k_inv, kc, Hkv, "k_inv");
+  check_kv_scale(v_inv, kc, Hkv, "v_inv");
+  check_hip(sentio_kv_store_fp8(
+                src_k.data_ptr(), src_v.data_ptr(), kc.data_ptr(),
+                vc.data_ptr(), rows.data_ptr<int>(), k_inv.data_ptr<float>(),
+                v_inv.data_ptr<float>(), (int)n, (int)kc.size(0), (int)Hkv,
+                (int)S_src, (int)S, (int)Smax, (int)D, stream()),
+            "kv_store_fp8");
+}
+
 torch::Tensor gemm_bf16(torch::Tensor a, torch::Tensor b) {
   check_bf16_cuda(a, "a");
   check_bf16_cuda(b, "b");
@@ -464,6 +565,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_cache", &flash_attn_cache);
   m.def("decode_attn", &decode_attn);
   m.def("decode_attn_fused", &decode_attn_fused);
+  m.def("decode_attn_fused_fp8", &decode_attn_fused_fp8);
+  m.def("kv_store_fp8", &kv_store_fp8);
   m.def("decode_attn_plan", &decode_attn_plan);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("skinny_gemm", &skinny_gemm);

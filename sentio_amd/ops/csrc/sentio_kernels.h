@@ -97,6 +97,23 @@ hipError_t sentio_decode_attn_fused(const void* qkv, void* kc, void* vc,
                                     int waves, int B, int H, int Hkv,
                                     int Smax, int D, float scale,
                                     hipStream_t stream);
+// as sentio_decode_attn_fused over uint8 (e4m3fn) caches; the four fp32
+// [Hkv] scale arrays sit between seq_lens and the workspaces, in the order
+// k_scale, v_scale, then the reciprocals k_inv, v_inv
+hipError_t sentio_decode_attn_fused_fp8(
+    const void* qkv, void* kc, void* vc, void* out, const float* cosT,
+    const float* sinT, const int* seq_lens, const float* k_scale,
+    const float* v_scale, const float* k_inv, const float* v_inv, float* ws_o,
+    float* ws_ml, int splits, int waves, int B, int H, int Hkv, int Smax,
+    int D, float scale, hipStream_t stream);
+// bf16 sources [n, Hkv, S_src, D] -> uint8 caches [B, Hkv, Smax, D] at
+// rows[i], first S rows; reciprocals only; dims are (n, B, Hkv, S_src, S,
+// Smax, D) — S_src and S sit BEFORE Smax
+hipError_t sentio_kv_store_fp8(const void* src_k, const void* src_v,
+                               void* dst_k, void* dst_v, const int* rows,
+                               const float* k_inv, const float* v_inv, int n,
+                               int B, int Hkv, int S_src, int S, int Smax,
+                               int D, hipStream_t stream);
 
 // ---- gemm.hip / blaslt.hip
 // B is [K, N] row-major; dims are (M, N, K)

@@ -318,6 +318,73 @@ def decode_attention_fused(
     return decode_attention(q, k_cache, v_cache, seq_lens + 1, scale)
 
 
+# ---- FP8 (e4m3fn) KV cache: uint8 storage, static fp32 scales per kv head
+FP8_E4M3_MAX = 448.0
+
+
+def _per_head(s: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """[Hkv] scale broadcast over x [..., Hkv, S, D]."""
+    s = torch.as_tensor(s, dtype=torch.float32, device=x.device)
+    return s.view(-1, 1, 1) if s.dim() == 1 else s
+
+
+def kv_quantize(x: torch.Tensor, inv: torch.Tensor) -> torch.Tensor:
+    """The quantisation spec: byte = RNE_e4m3fn(clamp(fp32(x) * inv, ±448)).
+    x [..., Hkv, S, D]; inv [Hkv] (or broadcastable) reciprocal scales.
+    Returns uint8.  The clamp is part of the spec: the bare cast yields NaN
+    above 464."""
+    y = (x.float() * _per_head(inv, x)).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def kv_dequantize(b: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """uint8 e4m3fn bytes [..., Hkv, S, D] * scale [Hkv] -> fp32."""
+    return b.view(torch.float8_e4m3fn).float() * _per_head(scale, b)
+
+
+def kv_store_fp8(src_k: torch.Tensor, src_v: torch.Tensor,
+                 k_cache: torch.Tensor, v_cache: torch.Tensor, rows, S: int,
+                 k_inv: torch.Tensor, v_inv: torch.Tensor) -> None:
+    """Quantising splice: the first S rows of src [n, Hkv, S_src, D] go to
+    cache[rows[i], :, :S] of the uint8 caches; rows outside [0, B) are
+    skipped."""
+    B = k_cache.shape[0]
+    rows = [int(r) for r in (rows.tolist() if isinstance(rows, torch.Tensor)
+                             else rows)]
+    for i, r in enumerate(rows):
+        if 0 <= r < B:
+            k_cache[r, :, :S] = kv_quantize(src_k[i, :, :S], k_inv)
+            v_cache[r, :, :S] = kv_quantize(src_v[i, :, :S], v_inv)
+
+
+def decode_attention_fused_fp8(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor,
+    k_scale: torch.Tensor, v_scale: torch.Tensor, k_inv: torch.Tensor,
+    v_inv: torch.Tensor, scale: float | None = None,
+) -> torch.Tensor:
+    """CPU reference of ops.decode_attention_fused_fp8: the new k/v row
+    (RoPE'd, in qkv's dtype) is quantised into the uint8 caches at row
+    seq_lens[b]; attention then runs over the DEQUANTISED seq_lens[b] + 1
+    keys, so the new token is seen as later steps will read it."""
+    B = qkv.shape[0]
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    H = qkv.shape[1] // D - 2 * Hkv
+    pos = seq_lens.long()
+    q = rope_apply(qkv[:, : H * D].view(B, 1, H, D), cos, sin,
+                   pos.view(B, 1)).view(B, H, D)
+    k_new = rope_apply(qkv[:, H * D : (H + Hkv) * D].view(B, 1, Hkv, D),
+                       cos, sin, pos.view(B, 1)).to(qkv.dtype)
+    v_new = qkv[:, (H + Hkv) * D :].view(B, 1, Hkv, D)
+    b_idx = torch.arange(B)
+    # [B, 1, Hkv, D] -> [B, Hkv, 1, D] for the per-head scales
+    k_cache[b_idx, :, pos] = kv_quantize(k_new.transpose(1, 2), k_inv)[:, :, 0]
+    v_cache[b_idx, :, pos] = kv_quantize(v_new.transpose(1, 2), v_inv)[:, :, 0]
+    return decode_attention(q, kv_dequantize(k_cache, k_scale),
+                            kv_dequantize(v_cache, v_scale), seq_lens + 1,
+                            scale)
+
+
 def swiglu_packed(gu: torch.Tensor) -> torch.Tensor:
     """gu [..., 2F] rows packed [gate | up] → silu(gate) * up, [..., F]."""
     f = gu.shape[-1] // 2

@@ -101,7 +101,8 @@ class ServiceContainer:
 
             return GeneratorEngine(self.settings.generator_model, device=self.device,
                                    dtype=self.settings.compute_dtype,
-                                   max_seq=self.settings.kv_cache_max_tokens)
+                                   max_seq=self.settings.kv_cache_max_tokens,
+                                   kv_cache_dtype=self.settings.kv_cache_dtype)
 
         return self._get("generator", make)
 
