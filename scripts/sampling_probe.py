@@ -6,6 +6,10 @@ Times, at B=64 and V in {128256, 152064} (fp32 logits resident on device):
   (c)  ops.sample_filtered k=50 p=0.9
   (d1) eager torch top-k/top-p     -- sort + cumsum + mask + Gumbel-argmax
   (d2) eager torch sample_rows     -- the continuous batcher's default code
+  (e)  ops.sample_slots            -- the slot loop's sampler (slot sampling
+       on) at S = 64 slots with 64, 8 and 1 of them active, for (k=0, p=1),
+       (k=50, p=0.9) and (k=0, p=0.9); same logits, identity addressing,
+       step counters advancing on the device as they do in the loop
 on two input families: "peaked" (LLM-like: 200 geometric ranks over a flat
 -30 tail) and "flat" (3*randn, a wide nucleus).
 
@@ -114,6 +118,18 @@ def main() -> None:
             kv = torch.full((B,), V, dtype=torch.int64, device=dev)
             seed = torch.arange(B, dtype=torch.int64, device=dev)
             step = torch.zeros(B, dtype=torch.int32, device=dev)
+            slot_variants = {}
+            tok = torch.zeros(B, dtype=torch.int64, device=dev)
+            for n_act in (64, 8, 1):
+                act = torch.zeros(B, dtype=torch.uint8, device=dev)
+                act[:n_act] = 1
+                for tag, kk, pp in (("k=0 p=1", k0, p1),
+                                    ("k=50 p=0.9", k50, p9),
+                                    ("k=0 p=0.9", k0, p9)):
+                    st = torch.zeros(B, dtype=torch.int32, device=dev)
+                    slot_variants[f"(e) sample_slots {tag} active={n_act}"] = (
+                        lambda kk=kk, pp=pp, st=st, act=act: ops.sample_slots(
+                            x, None, t, kk, pp, seed, st, act, tok))
             res = time_variants({
                 "(a) sample_token": lambda: ops.sample_token(x, 0.7, 1),
                 "(b) sample_filtered k=0 p=1": lambda: ops.sample_filtered(
@@ -128,6 +144,7 @@ def main() -> None:
                     x, t, kv, p9, rng),
                 "(d2) eager sample_rows": lambda: eager_sample_rows(
                     x, t, rng),
+                **slot_variants,
             })
             for name, (med, lo, hi) in res.items():
                 lines.append(f"| {kind} | {V} | {name} | {med:.1f} | "

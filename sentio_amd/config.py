@@ -106,6 +106,7 @@ class Settings:
     max_batch_size: int = 64          # continuous-batching slots (64 rows of KV ~ 68 GB at 8k ctx)
     dynamic_batching: bool = True           # batch concurrent /chat generations
     continuous_batching: bool = True        # requests join decode mid-flight
+    slot_sampling: bool = False             # top-k/top-p requests join the slot loop
     batch_wait_ms: float = 8.0
     device: str = "auto"                    # auto | cuda | cpu
 
@@ -158,6 +159,7 @@ class Settings:
         "max_batch_size": "MAX_BATCH_SIZE",
         "dynamic_batching": "DYNAMIC_BATCHING",
         "continuous_batching": "CONTINUOUS_BATCHING",
+        "slot_sampling": "SLOT_SAMPLING",
         "batch_wait_ms": "BATCH_WAIT_MS",
         "device": "SENTIO_DEVICE",
         "enable_metrics": "ENABLE_METRICS",

@@ -44,6 +44,72 @@ class SamplingParams:
                 or self.seed is not None)
 
 
+class SlotSampler:
+    """Per-slot sampling state of a continuous-batching session: the [S]
+    device arrays ops.sample_slots reads (temperature, top_k, top_p, seed,
+    active) and the step counter it advances.  admit() is the only
+    host-to-device traffic; a decode step is one kernel launch that writes
+    the loop's `cur` buffer in place."""
+
+    def __init__(self, engine: "GeneratorEngine", slots: int):
+        self.engine = engine
+        self.slots = int(slots)
+        dev = engine.device
+        S = self.slots
+        self.temperature = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.top_k = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(S, dtype=torch.float32, device=dev)
+        self.seed = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.step = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.active = torch.zeros(S, dtype=torch.uint8, device=dev)
+
+    @torch.inference_mode()
+    def admit(self, rows: list[int], params: list[SamplingParams]) -> None:
+        """Write each request's parameters into its slot: step = 0,
+        active = 1.  A request without a seed gets engine.derive_seed()."""
+        rows = [int(r) for r in rows]
+        if any(r < 0 or r >= self.slots for r in rows) \
+                or len(set(rows)) != len(rows):
+            raise ValueError(f"bad slot rows {rows} for {self.slots} slots")
+        if len(params) != len(rows):
+            raise ValueError(f"{len(params)} parameter sets for "
+                             f"{len(rows)} rows")
+        if not rows:
+            return
+        dev = self.engine.device
+        seeds = [int(p.seed) if p.seed is not None
+                 else self.engine.derive_seed() for p in params]
+        idx = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.temperature[idx] = torch.tensor(
+            [float(p.temperature) for p in params], dtype=torch.float32,
+            device=dev)
+        self.top_k[idx] = torch.tensor(
+            [int(p.top_k or 0) for p in params], dtype=torch.int32,
+            device=dev)
+        self.top_p[idx] = torch.tensor(
+            [float(p.top_p) for p in params], dtype=torch.float32,
+            device=dev)
+        self.seed[idx] = torch.tensor(seeds, dtype=torch.int64, device=dev)
+        self.step[idx] = 0
+        self.active[idx] = 1
+
+    @torch.inference_mode()
+    def release(self, row: int) -> None:
+        """The slot is free: later sample() calls skip it."""
+        self.active[int(row)] = 0
+
+    @torch.inference_mode()
+    def sample(self, logits: torch.Tensor, cur: torch.Tensor,
+               rows: list[int] | None = None) -> None:
+        """Draw one token per active slot into `cur` [S] int64, in place,
+        and advance those slots' step counters on the device.  With `rows`:
+        the admission call, logits [len(rows), V] scattered to those slots
+        (their step-0 draw; ops.sample_slots checks the list for range and
+        duplicates).  Without: the per-step call, logits [S, V]."""
+        ops.sample_slots(logits, rows, self.temperature, self.top_k,
+                         self.top_p, self.seed, self.step, self.active, cur)
+
+
 class _DecodeSession:
     """One (batch, cache-size) decode context: preallocated KV cache plus an
     optional hipGraph capture of the whole per-token decode step."""
@@ -339,6 +405,10 @@ class GeneratorEngine:
         slots persist across requests, so it must never come from (or be
         reset by) the shared _decode_session pool."""
         return _DecodeSession(self, slots, self.max_seq, self._use_graphs())
+
+    def make_slot_sampler(self, slots: int) -> SlotSampler:
+        """Per-slot sampling state for a slot session of `slots` rows."""
+        return SlotSampler(self, slots)
 
     @torch.inference_mode()
     def prefill_admission(self, prompts: list[str],

@@ -451,6 +451,70 @@ def sample_filtered(logits, temperature, top_k, top_p, seed, step):
     return torch_ref.sample_filtered(logits, t, k, p, sd, st)
 
 
+def _check_slot_array(t, name: str, n: int, dtype, device) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype \
+            or tuple(t.shape) != (n,) or not t.is_contiguous() \
+            or t.device != device:
+        raise ValueError(f"{name} must be a contiguous {dtype} [{n}] tensor "
+                         f"on {device}")
+
+
+def sample_slots(logits, slot, temperature, top_k, top_p, seed, step, active,
+                 tok) -> None:
+    """ops.sample_filtered over a table of S persistent slots, IN PLACE on
+    `step` and `tok` (the continuous batcher's per-step sampler).
+
+    logits f32 [R, V]; slot: None (R == S, row r is slot r), a Python
+    sequence (checked here for range and duplicates, then uploaded) or an
+    int32 [R] tensor on the logits' device (the kernel skips entries outside
+    [0, S); duplicates are the caller's to avoid: two rows on one slot race
+    on step[s]).  temperature f32, top_k i32, top_p f32, seed i64, step i32,
+    tok i64: contiguous [S] tensors of exactly these dtypes on the logits'
+    device -- nothing is converted, a copy could not be written back.
+    active: None or uint8 [S]; a slot with active[s] == 0 is skipped.
+
+    For every sampled row: tok[s] = the token ops.sample_filtered draws from
+    logits[r] with slot s's parameters at step[s], then step[s] += 1.
+    Skipped slots keep tok[s] and step[s].  CPU and GPU agree on the support
+    and on greedy rows, not on the stochastic pick."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 \
+            or logits.dtype != torch.float32 or logits.numel() == 0:
+        raise ValueError("logits must be a non-empty float32 [R, V] tensor")
+    if not isinstance(tok, torch.Tensor) or tok.dim() != 1 \
+            or tok.numel() == 0:
+        raise ValueError("tok must be a non-empty int64 [S] tensor")
+    R, S, dev = logits.shape[0], tok.shape[0], logits.device
+    _check_slot_array(tok, "tok", S, torch.int64, dev)
+    _check_slot_array(temperature, "temperature", S, torch.float32, dev)
+    _check_slot_array(top_k, "top_k", S, torch.int32, dev)
+    _check_slot_array(top_p, "top_p", S, torch.float32, dev)
+    _check_slot_array(seed, "seed", S, torch.int64, dev)
+    _check_slot_array(step, "step", S, torch.int32, dev)
+    if active is not None:
+        _check_slot_array(active, "active", S, torch.uint8, dev)
+    if slot is None:
+        if R != S:
+            raise ValueError(f"without a slot table logits must have one row "
+                             f"per slot: {R} rows for {S} slots")
+    elif isinstance(slot, torch.Tensor):
+        _check_slot_array(slot, "slot", R, torch.int32, dev)
+    else:
+        slot = [int(s) for s in slot]
+        if len(slot) != R:
+            raise ValueError(f"{len(slot)} slots for {R} logits rows")
+        if any(s < 0 or s >= S for s in slot):
+            raise ValueError(f"slots {slot} outside [0, {S})")
+        if len(set(slot)) != len(slot):
+            raise ValueError(f"duplicate slots in {slot}")
+        slot = torch.tensor(slot, dtype=torch.int32, device=dev)
+    if _on_gpu(logits):
+        _require_hip().sample_slots(logits.contiguous(), slot, temperature,
+                                    top_k, top_p, seed, step, active, tok)
+        return
+    torch_ref.sample_slots(logits, slot, temperature, top_k, top_p, seed,
+                           step, active, tok)
+
+
 def skinny_gemm(x, w):
     """Skinny decode GEMM: x [M<=32, K] @ W^T with W stored [N, K] row-major
     (TN layout) → [M, N] bf16.  Streams W rows straight to MFMA A-fragments.
@@ -495,5 +559,5 @@ def gemm_bf16(a, b):
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
-    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
+    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_slots", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -198,6 +198,46 @@ torch::Tensor sample_filtered(torch::Tensor logits, torch::Tensor temperature,
   return out;
 }
 
+// In place on step and tok, so nothing here may convert or copy: every
+// tensor must already have its kernel dtype and be contiguous on the GPU.
+void sample_slots(torch::Tensor logits, c10::optional<torch::Tensor> slot,
+                  torch::Tensor temperature, torch::Tensor top_k,
+                  torch::Tensor top_p, torch::Tensor seed, torch::Tensor step,
+                  c10::optional<torch::Tensor> active, torch::Tensor tok) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+              logits.scalar_type() == torch::kFloat && logits.is_contiguous(),
+              "logits must be a contiguous f32 [R,V] GPU tensor");
+  const long R = logits.size(0);
+  const long S = tok.numel();
+  TORCH_CHECK(R > 0 && S > 0 && logits.size(1) > 0,
+              "logits and slots must be non-empty");
+  auto slot_arr = [&](const torch::Tensor& t, torch::ScalarType dt, long n,
+                      const char* name) {
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.scalar_type() == dt &&
+                t.is_contiguous() && t.device() == logits.device(), name,
+                " must be a contiguous [", n, "] tensor of its kernel dtype "
+                "on the logits' device");
+  };
+  slot_arr(tok, torch::kLong, S, "tok");
+  slot_arr(temperature, torch::kFloat, S, "temperature");
+  slot_arr(top_k, torch::kInt, S, "top_k");
+  slot_arr(top_p, torch::kFloat, S, "top_p");
+  slot_arr(seed, torch::kLong, S, "seed");
+  slot_arr(step, torch::kInt, S, "step");
+  if (slot.has_value()) slot_arr(*slot, torch::kInt, R, "slot");
+  else TORCH_CHECK(R == S, "without a slot table logits must be [S,V]");
+  if (active.has_value()) slot_arr(*active, torch::kByte, S, "active");
+  check_hip(sentio_sample_slots(
+      logits.data_ptr<float>(),
+      slot.has_value() ? slot->data_ptr<int>() : nullptr,
+      temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p.data_ptr<float>(), (const long*)seed.data_ptr<int64_t>(),
+      step.data_ptr<int>(),
+      active.has_value() ? active->data_ptr<uint8_t>() : nullptr,
+      (long*)tok.data_ptr<int64_t>(), R, (int)S, (int)logits.size(1),
+      stream()), "sample_slots");
+}
+
 torch::Tensor cosine_scores(torch::Tensor q, torch::Tensor mat) {
   TORCH_CHECK(q.is_cuda() && mat.is_cuda(), "must be on GPU");
   TORCH_CHECK(q.scalar_type() == mat.scalar_type(), "q/mat dtype mismatch");
@@ -559,6 +599,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_token", &sample_token);
   m.def("sample_support", &sample_support);
   m.def("sample_filtered", &sample_filtered);
+  m.def("sample_slots", &sample_slots);
   m.def("cosine_scores", &cosine_scores);
   m.def("bm25_score", &bm25_score);
   m.def("flash_attn", &flash_attn);

@@ -5,6 +5,9 @@
 //   sample_filtered: the same first phase, then a Gumbel-argmax over the kept
 //                    set {v : logit_v >= tau} with noise hashed from
 //                    (seed_b, step_b, v) -- never from the row index or B.
+//   sample_slots   : sample_filtered over a slot table: row r samples with
+//                    the parameters of slot[r], skips free slots, writes the
+//                    token into tok[slot] and advances step[slot] in place.
 //
 // One 1024-thread block per row; nothing is sorted.  tau is found by a radix
 // descent (4 levels x 8 bits) on an order-preserving uint32 key of the RAW
@@ -243,21 +246,20 @@ __device__ __forceinline__ unsigned sf_hash(unsigned v, unsigned k0,
   return x;
 }
 
-template <bool SAMPLE>
-__global__ __launch_bounds__(SF_THREADS) void sample_filtered_kernel(
-    const float* __restrict__ logits, const float* __restrict__ temperature,
-    const int* __restrict__ top_k, const float* __restrict__ top_p,
-    const long* __restrict__ seed, const int* __restrict__ step,
-    float* __restrict__ tau_out, int* __restrict__ count_out,
-    long* __restrict__ tok_out, int V) {
-  __shared__ SfShared sh;
-  const long b = blockIdx.x;
-  const float* lb = logits + b * (long)V;
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const float T = temperature[b];
-  const int k = top_k[b];
-  const float p = top_p[b];
+// What phase 1 leaves for phase 2: the row max, 1/T (1 when greedy), the
+// threshold logit and whether the row is greedy.  Block-uniform.
+struct SfRow {
+  float xmax, invT, tau;
+  bool greedy;
+};
 
+// Pre-pass and phase 1: row statistics, then the threshold logit tau of the
+// kept set {v : logit_v >= tau} after top-k then top-p.  Whole block; every
+// thread returns the same SfRow.
+__device__ __forceinline__ SfRow sf_threshold(const float* __restrict__ lb,
+                                              int V, float T, int k, float p,
+                                              SfShared& sh) {
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   // ---- pre-pass: row max, smallest finite logit, number of finite logits
   float xmax = -INFINITY, xmin = INFINITY;
   int nfin = 0;
@@ -316,26 +318,22 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filtered_kernel(
       tau = sf_unkey(key_p);
     }
   }
+  return SfRow{xmax, invT, tau, greedy};
+}
 
-  if (!SAMPLE) {
-    int cnt = 0;
-    sf_foreach(lb, V, [&](float x, int) { cnt += (x >= tau) ? 1 : 0; });
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
-    if (lane == 0) sh.redi[wid] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int c = 0;
-      for (int w = 0; w < SF_WAVES; ++w) c += sh.redi[w];
-      tau_out[b] = tau;
-      count_out[b] = c;
-    }
-    return;
-  }
-
-  // ---- phase 2: Gumbel-argmax over the kept set (plain argmax when greedy)
-  const u64 rk = sf_mix64((u64)seed[b] ^
-                          sf_mix64((u64)(unsigned)step[b] + 0x9E3779B97F4A7C15ull));
+// Phase 2: Gumbel-argmax over the kept set (plain argmax when greedy), noise
+// hashed from (seed, step, v).  Whole block; the token is valid on thread 0
+// only, and nothing follows the function's one block barrier but thread 0's
+// scan of the per-wave winners.
+__device__ __forceinline__ long sf_gumbel_argmax(const float* __restrict__ lb,
+                                                 int V, const SfRow& r,
+                                                 long seed, int step,
+                                                 SfShared& sh) {
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  const float xmax = r.xmax, invT = r.invT, tau = r.tau;
+  const bool greedy = r.greedy;
+  const u64 rk = sf_mix64((u64)seed ^
+                          sf_mix64((u64)(unsigned)step + 0x9E3779B97F4A7C15ull));
   const unsigned k0 = (unsigned)rk, k1 = (unsigned)(rk >> 32);
   float best = -INFINITY;
   int besti = 0x7fffffff;
@@ -365,15 +363,78 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filtered_kernel(
   }
   if (lane == 0) { sh.redf[wid] = best; sh.redi[wid] = besti; }
   __syncthreads();
+  int bi = 0;
   if (threadIdx.x == 0) {
     float bv = sh.redf[0];
-    int bi = sh.redi[0];
+    bi = sh.redi[0];
     for (int w = 1; w < SF_WAVES; ++w)
       if (sh.redf[w] > bv || (sh.redf[w] == bv && sh.redi[w] < bi)) {
         bv = sh.redf[w];
         bi = sh.redi[w];
       }
-    tok_out[b] = (bi < V) ? bi : 0;
+  }
+  return (bi < V) ? bi : 0;
+}
+
+template <bool SAMPLE>
+__global__ __launch_bounds__(SF_THREADS) void sample_filtered_kernel(
+    const float* __restrict__ logits, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const float* __restrict__ top_p,
+    const long* __restrict__ seed, const int* __restrict__ step,
+    float* __restrict__ tau_out, int* __restrict__ count_out,
+    long* __restrict__ tok_out, int V) {
+  __shared__ SfShared sh;
+  const long b = blockIdx.x;
+  const float* lb = logits + b * (long)V;
+  const SfRow r = sf_threshold(lb, V, temperature[b], top_k[b], top_p[b], sh);
+
+  if (!SAMPLE) {
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const float tau = r.tau;
+    int cnt = 0;
+    sf_foreach(lb, V, [&](float x, int) { cnt += (x >= tau) ? 1 : 0; });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
+    if (lane == 0) sh.redi[wid] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int c = 0;
+      for (int w = 0; w < SF_WAVES; ++w) c += sh.redi[w];
+      tau_out[b] = tau;
+      count_out[b] = c;
+    }
+    return;
+  }
+
+  const long tok = sf_gumbel_argmax(lb, V, r, seed[b], step[b], sh);
+  if (threadIdx.x == 0) tok_out[b] = tok;
+}
+
+// The slot loop's sampler: logits row r belongs to slot s = slot ? slot[r] : r
+// of S persistent slots, each with its own (T, top_k, top_p, seed) and a step
+// counter that lives on the device.  A row whose slot is outside [0, S) or
+// whose slot is inactive returns before any barrier or store (s is
+// block-uniform).  Otherwise: sample_filtered's arithmetic at step[s], token
+// to tok[s], step[s] + 1 to step[s].  Two rows on one slot would race on
+// step[s]: callers pass each slot at most once.
+__global__ __launch_bounds__(SF_THREADS) void sample_slots_kernel(
+    const float* __restrict__ logits, const int* __restrict__ slot,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, const long* __restrict__ seed,
+    int* __restrict__ step, const unsigned char* __restrict__ active,
+    long* __restrict__ tok, int S, int V) {
+  __shared__ SfShared sh;
+  const long row = blockIdx.x;
+  const int s = slot ? slot[row] : (int)row;
+  if (s < 0 || s >= S) return;
+  if (active && active[s] == 0) return;
+  const int st = step[s];
+  const float* lb = logits + row * (long)V;
+  const SfRow r = sf_threshold(lb, V, temperature[s], top_k[s], top_p[s], sh);
+  const long t = sf_gumbel_argmax(lb, V, r, seed[s], st, sh);
+  if (threadIdx.x == 0) {
+    tok[s] = t;
+    step[s] = st + 1;
   }
 }
 
@@ -400,6 +461,21 @@ hipError_t sentio_sample_filtered(const float* logits, const float* temperature,
   hipLaunchKernelGGL((sample_filtered_kernel<true>), dim3((unsigned)B),
                      dim3(SF_THREADS), 0, stream, logits, temperature, top_k,
                      top_p, seed, step, (float*)nullptr, (int*)nullptr, out, V);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_sample_slots(const float* logits, const int* slot,
+                               const float* temperature, const int* top_k,
+                               const float* top_p, const long* seed, int* step,
+                               const unsigned char* active, long* tok, long R,
+                               int S, int V, hipStream_t stream) {
+  if (R <= 0 || S <= 0 || V <= 0 || R > 0x7fffffffL) return hipErrorInvalidValue;
+  // without a slot table row r is slot r: every row needs a slot of its own
+  if (!slot && R != S) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sample_slots_kernel, dim3((unsigned)R), dim3(SF_THREADS),
+                     0, stream, logits, slot, temperature, top_k, top_p, seed,
+                     step, active, tok, S, V);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

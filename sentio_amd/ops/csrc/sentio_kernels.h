@@ -48,6 +48,15 @@ hipError_t sentio_sample_filtered(const float* logits, const float* temperature,
                                   const int* top_k, const float* top_p,
                                   const long* seed, const int* step, long* out,
                                   long B, int V, hipStream_t stream);
+// logits [R,V]; slot [R] or null (null: R == S, row r is slot r); the
+// parameter arrays, step (in/out) and tok (in/out) are [S]; active [S] or
+// null; dims are (R, S, V).  Rows whose slot is outside [0,S) or inactive
+// write nothing
+hipError_t sentio_sample_slots(const float* logits, const int* slot,
+                               const float* temperature, const int* top_k,
+                               const float* top_p, const long* seed, int* step,
+                               const unsigned char* active, long* tok, long R,
+                               int S, int V, hipStream_t stream);
 
 // ---- retrieval.hip
 // index matrix first, queries second; dims are (N, D, B)

@@ -284,6 +284,30 @@ def sample_filtered(logits: torch.Tensor, temperature, top_k, top_p, seed,
     return out
 
 
+def sample_slots(logits: torch.Tensor, slot, temperature, top_k, top_p, seed,
+                 step: torch.Tensor, active, tok: torch.Tensor) -> None:
+    """sample_filtered over a slot table, in place on `step` and `tok`.
+
+    logits [R, V]; slot [R] ints or None (None: R == S, row r is slot r);
+    temperature / top_k / top_p / seed / step / tok are [S]; active [S] or
+    None.  Row r belongs to slot s = slot[r].  A slot outside [0, S) or with
+    active[s] == 0 is skipped: tok[s] and step[s] keep their values.
+    Otherwise tok[s] = sample_filtered(logits[r], params[s], seed[s],
+    step[s]) and step[s] += 1."""
+    R, S = logits.shape[0], tok.shape[0]
+    slots = list(range(R)) if slot is None \
+        else [int(s) for s in torch.as_tensor(slot).flatten().tolist()]
+    if len(slots) != R:
+        raise ValueError(f"{len(slots)} slots for {R} logits rows")
+    for r, s in enumerate(slots):
+        if s < 0 or s >= S or (active is not None and int(active[s]) == 0):
+            continue
+        tok[s] = sample_filtered(logits[r:r + 1], temperature[s:s + 1],
+                                 top_k[s:s + 1], top_p[s:s + 1],
+                                 seed[s:s + 1], step[s:s + 1])[0]
+        step[s] += 1
+
+
 def decode_qkv_prep(
     qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor

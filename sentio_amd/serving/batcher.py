@@ -12,13 +12,15 @@ Three coalescing layers live here:
   batching: requests join a persistent slot-session decode loop at step
   boundaries (admission prefill on a side stream, per-row seq_lens and
   per-row-temperature sampling), stream per step, and free their slot the
-  moment they finish — no wave barrier.
+  moment they finish — no wave barrier.  With `slot_sampling=True` the loop
+  samples every resident request through ops.sample_slots, so top-k /
+  top-p requests join it too.
 * `DynamicBatcher` (CONTINUOUS_BATCHING=0 fallback, and the mock-engine
   path) — wave batching: group by sampling params, keep collecting while
   the engine runs the previous batch, run ONE batched generate.  It also
-  serves, beside the continuous loop, the requests that set top-k /
-  top-p / seed (`_SampledItem`): the slot loop samples with per-row
-  temperature only.
+  serves, beside the continuous loop, the requests the loop does not take
+  (`_SampledItem`): seeded ones always, and top-k / top-p ones unless
+  `slot_sampling` is on.
 * `MicroBatcher` + `BatchedEncoder`/`BatchedReranker` — concurrent
   single-query embeds / rerank pair scores coalesce into one engine
   forward each.
@@ -59,8 +61,9 @@ class _Item:
 @dataclass
 class _SampledItem(_Item):
     """A request with nucleus-sampling controls (top-k / top-p / seed).
-    Only the wave batcher carries these; default requests stay plain
-    `_Item`s and group exactly as before."""
+    The wave batcher carries these, and so does the continuous batcher with
+    slot sampling on; default requests stay plain `_Item`s and group
+    exactly as before."""
     top_k: int = 0
     top_p: float = 1.0
     seed: int | None = None
@@ -88,6 +91,16 @@ def _make_item(prompt: str, max_new_tokens: int, temperature: float,
                             top_p=top_p, seed=seed)
     return _Item(prompt, max_new_tokens, float(temperature), stop_on_eos,
                  stream_q=stream_q)
+
+
+def _slot_params(item: _Item):
+    """The SamplingParams a slot-loop request brings; a default request is
+    (T, top_k=0, top_p=1, no seed)."""
+    from sentio_amd.engines.generator import SamplingParams
+
+    return SamplingParams(item.temperature, getattr(item, "top_k", 0),
+                          getattr(item, "top_p", 1.0),
+                          getattr(item, "seed", None))
 
 
 def _sampling_only(kwargs: dict) -> dict:
@@ -282,12 +295,26 @@ class ContinuousBatcher:
     Slot safety: free rows keep riding the (graph-replayed) decode step
     with garbage inputs — their seq_lens are re-zeroed every step so the
     KV write position can never run off the cache end, and their outputs
-    are never read."""
+    are never read.
 
-    def __init__(self, generator, slots: int = 32, admit_max: int = 8):
+    slot_sampling=True: every resident request, default ones included,
+    samples through a SlotSampler (ops.sample_slots: per-slot temperature /
+    top-k / top-p / seed, step counters on the device, tokens written
+    straight into the loop's `cur`), so requests with top_k / top_p join
+    the loop.  A seed is honoured, but a slot-loop request's logits come
+    from a different row of a shared batch on every run and the GEMMs do
+    not promise bitwise-equal rows across row positions: a seed does NOT
+    make a slot-loop answer reproducible (ContinuousGenerator keeps seeded
+    requests on the wave path for that reason).  Off (the default): the
+    loop samples with per-row temperature only, through sample_rows, and
+    rejects requests that set top_k / top_p / seed."""
+
+    def __init__(self, generator, slots: int = 32, admit_max: int = 8,
+                 slot_sampling: bool = False):
         self.generator = generator
         self.n_slots = slots
         self.admit_max = admit_max
+        self.slot_sampling = bool(slot_sampling)
         self._q: queue.Queue[_Item] = queue.Queue()
         self._stop = threading.Event()
         self._thread: threading.Thread | None = None
@@ -296,19 +323,35 @@ class ContinuousBatcher:
                       "max_concurrent": 0, "admissions": 0}
 
     # ----- caller side -----
+    def _item(self, prompt, max_new_tokens, temperature, stop_on_eos,
+              stream_q, top_k, top_p, seed) -> _Item:
+        item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
+                          stream_q=stream_q, top_k=top_k, top_p=top_p,
+                          seed=seed)
+        if isinstance(item, _SampledItem) and not self.slot_sampling:
+            raise ValueError(
+                "top_k / top_p / seed need ContinuousBatcher("
+                "slot_sampling=True): the default slot loop samples with "
+                "per-row temperature only")
+        return item
+
     def generate(self, prompt: str, max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
-                 timeout_s: float = 300.0) -> str:
+                 timeout_s: float = 300.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: int | None = None) -> str:
+        item = self._item(prompt, max_new_tokens, temperature, stop_on_eos,
+                          None, top_k, top_p, seed)
         self.start()
-        item = _Item(prompt, max_new_tokens, float(temperature), stop_on_eos)
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
 
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
-                        temperature: float = 0.3, timeout_s: float = 300.0):
+                        temperature: float = 0.3, timeout_s: float = 300.0,
+                        top_k: int = 0, top_p: float = 1.0,
+                        seed: int | None = None):
+        item = self._item(prompt, max_new_tokens, temperature, True,
+                          queue.Queue(), top_k, top_p, seed)
         self.start()
-        item = _Item(prompt, max_new_tokens, float(temperature), True,
-                     stream_q=queue.Queue())
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
 
@@ -462,11 +505,17 @@ class ContinuousBatcher:
         cur = torch.zeros(self.n_slots, dtype=torch.int64, device=dev)
         temps = torch.zeros(self.n_slots, device=dev)
         free_mask = torch.ones(self.n_slots, dtype=torch.bool, device=dev)
+        # slot sampling: per-slot (T, top_k, top_p, seed, step) on the
+        # device; None keeps the per-row-temperature sample_rows path
+        sampler = (gen.make_slot_sampler(self.n_slots)
+                   if self.slot_sampling else None)
 
         def finish(r: int, reason: str) -> None:
             s = state[r]
             state[r] = None
             free_mask[r] = True
+            if sampler is not None:
+                sampler.release(r)
             self.stats["completed"] += 1
             it = s["item"]
             if it.stream_q is not None:
@@ -514,9 +563,18 @@ class ContinuousBatcher:
                                                          idx=take)
                         items = [want[j] for j in take]
                         lens_host = [pre["lens_host"][j] for j in take]
-                        t_adm = torch.tensor([it.temperature for it in items],
-                                             device=dev)
-                        tok0 = gen.sample_rows(logits, t_adm).cpu().tolist()
+                        if sampler is None:
+                            t_adm = torch.tensor(
+                                [it.temperature for it in items], device=dev)
+                            tok0 = gen.sample_rows(logits,
+                                                   t_adm).cpu().tolist()
+                        else:
+                            # the step-0 draw, scattered into cur[rows]
+                            sampler.admit(rows, [_slot_params(it)
+                                                 for it in items])
+                            sampler.sample(logits, cur, rows=rows)
+                            cur_host = cur.cpu().tolist()
+                            tok0 = [cur_host[r] for r in rows]
                         for j, (r, it) in enumerate(zip(rows, items)):
                             # decode may never write past the slot cache:
                             # remaining steps clamp to Smax - prompt_len - 1
@@ -526,8 +584,9 @@ class ContinuousBatcher:
                                         "remaining": min(it.max_new_tokens,
                                                          cap)}
                             free_mask[r] = False
-                            temps[r] = it.temperature
-                            cur[r] = tok0[j]
+                            if sampler is None:
+                                temps[r] = it.temperature
+                                cur[r] = tok0[j]
                             feed(r, tok0[j])
                         self.stats["requests"] += len(items)
                         self.stats["admissions"] += 1
@@ -536,6 +595,10 @@ class ContinuousBatcher:
                             sum(st_ is not None for st_ in state))
                     except Exception as exc:
                         pending = None
+                        if sampler is not None:   # admitted, never resident
+                            for r in rows:
+                                if state[r] is None:
+                                    sampler.release(r)
                         for it in want:
                             if it.stream_q is not None:
                                 it.stream_q.put(None)
@@ -549,8 +612,12 @@ class ContinuousBatcher:
             sess.cache.seq_lens.masked_fill_(free_mask, 0)
             with _step_timer.measure():   # lazy HIP events, no sync
                 logits = gen.decode_step_session(sess, cur)
-            toks = gen.sample_rows(logits, temps)
-            cur.copy_(toks)
+            if sampler is None:
+                toks = gen.sample_rows(logits, temps)
+                cur.copy_(toks)
+            else:
+                sampler.sample(logits, cur)   # writes cur in place
+                toks = cur
             self.stats["steps"] += 1
             toks_host = toks.cpu().tolist()
             for r in range(self.n_slots):
@@ -589,17 +656,35 @@ class ContinuousGenerator:
     """Generator frontend for continuous batching: single-prompt calls and
     streams join the slot loop; multi-prompt (bench-style) calls pass
     through to the raw engine (they interleave with the loop between
-    steps via the engine lock)."""
+    steps via the engine lock).
 
-    def __init__(self, raw, slots: int = 32):
+    slot_sampling=False (default): requests with top-k / top-p / seed do
+    not join the slot loop (it samples with per-row temperature only); they
+    run as waves of the raw engine through `sampled_batcher`, like
+    multi-prompt calls do.  A wave holds the engine lock for its whole
+    generation, the loop takes it per step: the loop stalls while a wave
+    decodes.
+
+    slot_sampling=True: the loop samples per slot (ops.sample_slots), and
+    single-prompt requests that set top_k and/or top_p and NO seed join it.
+    Seeded requests stay on the wave path in both modes: a seed promises
+    the same answer whatever else shares the engine, and in the slot loop a
+    request's logits come from a different row of a shared batch on each
+    run, where nothing guarantees bitwise-equal GEMM rows across row
+    positions -- the loop cannot keep that promise."""
+
+    def __init__(self, raw, slots: int = 32, slot_sampling: bool = False):
         self.raw = raw
-        self.batcher = ContinuousBatcher(raw, slots=slots)
-        # Requests with top-k / top-p / seed do not join the slot loop (it
-        # samples with per-row temperature only): they run as waves of the
-        # raw engine through a DynamicBatcher, like multi-prompt calls do.
-        # A wave holds the engine lock for its whole generation, the loop
-        # takes it per step: the loop stalls while a wave decodes.
+        self.slot_sampling = bool(slot_sampling)
+        self.batcher = ContinuousBatcher(raw, slots=slots,
+                                         slot_sampling=self.slot_sampling)
         self.sampled_batcher = DynamicBatcher(raw, max_batch=slots)
+
+    def _joins_loop(self, sampling: dict) -> bool:
+        """Whether a single-prompt request with these sampling keywords
+        ({} for a default one) goes to the slot loop."""
+        return not sampling or (self.slot_sampling
+                                and "seed" not in sampling)
 
     def generate(self, prompts: list[str], max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
@@ -609,7 +694,7 @@ class ContinuousGenerator:
                                      temperature=temperature,
                                      stop_on_eos=stop_on_eos, **kwargs)
         sampling = _sampling_only(kwargs)
-        if sampling:
+        if not self._joins_loop(sampling):
             return [self.sampled_batcher.generate(
                 prompts[0], max_new_tokens=max_new_tokens,
                 temperature=temperature, stop_on_eos=stop_on_eos,
@@ -617,18 +702,19 @@ class ContinuousGenerator:
         return [self.batcher.generate(prompts[0],
                                       max_new_tokens=max_new_tokens,
                                       temperature=temperature,
-                                      stop_on_eos=stop_on_eos)]
+                                      stop_on_eos=stop_on_eos, **sampling)]
 
     def stream(self, prompt: str, max_new_tokens: int = 128,
                temperature: float = 0.3, **kwargs):
         sampling = _sampling_only(kwargs)
-        if sampling:
+        if not self._joins_loop(sampling):
             return self.sampled_batcher.generate_stream(
                 prompt, max_new_tokens=max_new_tokens,
                 temperature=temperature, **sampling)
         return self.batcher.generate_stream(prompt,
                                             max_new_tokens=max_new_tokens,
-                                            temperature=temperature)
+                                            temperature=temperature,
+                                            **sampling)
 
     def __getattr__(self, name):
         return getattr(self.raw, name)

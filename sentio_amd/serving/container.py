@@ -120,7 +120,8 @@ class ServiceContainer:
                 from sentio_amd.serving.batcher import ContinuousGenerator
 
                 return ContinuousGenerator(
-                    raw, slots=self.settings.max_batch_size)
+                    raw, slots=self.settings.max_batch_size,
+                    slot_sampling=self.settings.slot_sampling)
             if not self.settings.dynamic_batching:
                 return raw
             from sentio_amd.serving.batcher import BatchedGenerator
