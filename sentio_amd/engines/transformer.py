@@ -237,6 +237,27 @@ class Transformer:
             ops.decode_attention_bmm
             if os.environ.get("SENTIO_DECODE_ATTN") == "bmm"
             else ops.decode_attention)
+        # Decode projections onto the model dimension (wo, down), fixed for
+        # the model's lifetime for the same reason: the split-K hand GEMM
+        # whose fp32 partials the following residual RMSNorm sums
+        # (ops.linear_splitk + ops.rmsnorm_residual_partials), or hipBLASLt
+        # + rmsnorm_residual.  The hand pair needs the GPU, no TP (the
+        # row-parallel all-reduce wants the bf16 output), at most 32 rows
+        # and a shape ops.decode_gemm_plan accepts.  SENTIO_DECODE_GEMM=lt
+        # keeps the library path; wo / down route only that projection.
+        self.splitk_wo, self.splitk_down = self._plan_decode_gemm()
+
+    def _plan_decode_gemm(self) -> tuple[bool, bool]:
+        mode = os.environ.get("SENTIO_DECODE_GEMM", "auto")
+        if (mode == "lt" or self.tp.enabled or not ops.hip_available()
+                or not str(self.device).startswith("cuda")
+                or self.dtype != torch.bfloat16):
+            return False, False
+        cfg = self.cfg
+        wo = ops.decode_gemm_plan(32, cfg.dim,
+                                  self.h_local * cfg.head_dim)[0] > 0
+        down = ops.decode_gemm_plan(32, cfg.dim, cfg.ffn_dim)[0] > 0
+        return wo and mode != "down", down and mode != "wo"
 
     # ----- core blocks -----
     def _attn(self, x: torch.Tensor, layer: dict, pos: torch.Tensor,
@@ -299,8 +320,9 @@ class Transformer:
     def _ffn(self, x: torch.Tensor, layer: dict) -> torch.Tensor:
         B, S, d = x.shape
         # measured: hipBLASLt's TN path beats the hand skinny_gemm kernel on
-        # the decode gate_up shape in context (63 vs ~87 us at B=32); decode
-        # rows additionally go through the autotuned-algorithm binding
+        # the decode gate_up shape in context (52 us, 4.5 TB/s, at B=32 with
+        # the autotuned algorithm; the hand kernel took ~87 us), so decode
+        # rows go through the autotuned-algorithm binding
         rows = B * S
         xx = x.view(rows, d)
         if rows <= 64 and self.device != "cpu":
@@ -349,6 +371,17 @@ class Transformer:
                      layer_idx: int,
                      attn_lens: torch.Tensor | None) -> torch.Tensor:
         B = normed.shape[0]
+        out = self._attn_decode_heads(normed, layer, cache, layer_idx,
+                                      attn_lens)
+        out = linear_row_parallel(out, layer["wo"], self.tp,
+                                  linear=ops.lt_linear)
+        return out.view(B, 1, self.cfg.dim)
+
+    def _attn_decode_heads(self, normed: torch.Tensor, layer: dict,
+                           cache: KVCache, layer_idx: int,
+                           attn_lens: torch.Tensor | None) -> torch.Tensor:
+        """Decode attention up to the output projection: [B, H_local * hd]."""
+        B = normed.shape[0]
         d = self.cfg.dim
         hd = self.cfg.head_dim
         qkv = ops.lt_linear(normed.view(B, d), layer["wqkv"])
@@ -370,9 +403,7 @@ class Transformer:
                                     self.rope_sin, cache.seq_lens)
             out = self.decode_attn(q, cache.k[layer_idx], cache.v[layer_idx],
                                    attn_lens, self.scale)
-        out = linear_row_parallel(out.view(B, self.h_local * hd),
-                                  layer["wo"], self.tp, linear=ops.lt_linear)
-        return out.view(B, 1, d)
+        return out.view(B, self.h_local * hd)
 
     def forward_decode(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
         """One-token decode: tokens [B, 1] → hidden [B, 1, dim].  RoPE and
@@ -389,12 +420,28 @@ class Transformer:
         # path needs the key count
         attn_lens = (None if self._decode_fused(x) else cache.seq_lens + 1)
         normed = ops.rmsnorm(x, layers[0]["attn_norm"], eps)
+        # B is fixed per captured graph, so this is a per-graph constant
+        sk_wo = self.splitk_wo and B <= 32
+        sk_down = self.splitk_down and B <= 32
         for i, layer in enumerate(layers):
-            a = self._attn_decode(normed, layer, cache, i, attn_lens)
-            normed, x = ops.rmsnorm_residual(a, x, layer["ffn_norm"], eps)
-            f = self._ffn(normed, layer)
+            if sk_wo:
+                a = ops.linear_splitk(
+                    self._attn_decode_heads(normed, layer, cache, i,
+                                            attn_lens), layer["wo"])
+                normed, x = ops.rmsnorm_residual_partials(
+                    a, x, layer["ffn_norm"], eps)
+            else:
+                a = self._attn_decode(normed, layer, cache, i, attn_lens)
+                normed, x = ops.rmsnorm_residual(a, x, layer["ffn_norm"], eps)
             w_next = layers[i + 1]["attn_norm"] if i + 1 < n else self.w.final_norm
-            normed, x = ops.rmsnorm_residual(f, x, w_next, eps)
+            if sk_down:
+                gu = ops.lt_linear(normed.view(B, self.cfg.dim),
+                                   layer["w_gate_up"])
+                f = ops.linear_splitk(ops.swiglu_packed(gu), layer["w_down"])
+                normed, x = ops.rmsnorm_residual_partials(f, x, w_next, eps)
+            else:
+                f = self._ffn(normed, layer)
+                normed, x = ops.rmsnorm_residual(f, x, w_next, eps)
         return normed
 
     # ----- decoder-specific -----

@@ -67,6 +67,18 @@ def rmsnorm_residual(x, residual, weight, eps: float = 1e-5):
     return torch_ref.rmsnorm_residual(x, residual, weight, eps)
 
 
+def rmsnorm_residual_partials(part, residual, weight, eps: float = 1e-5):
+    """ops.rmsnorm_residual with the projection given as split-K partials:
+    part fp32 [S, rows, D] (ops.linear_splitk), summed in increasing s, plus
+    residual [..., D] → (y, h) shaped like residual.  The sum never rounds
+    to bf16 before the residual add."""
+    if _on_gpu(part):
+        y, h = _require_hip().rmsnorm_residual_partials(
+            part.contiguous(), residual.contiguous(), weight.contiguous(), eps)
+        return y, h
+    return torch_ref.rmsnorm_residual_partials(part, residual, weight, eps)
+
+
 def rope_apply(x, cos, sin, pos):
     if _on_gpu(x):
         return _require_hip().rope_apply(
@@ -524,6 +536,30 @@ def skinny_gemm(x, w):
     return torch.nn.functional.linear(x.float(), w.float()).to(x.dtype)
 
 
+def decode_gemm_plan(M: int, N: int, K: int) -> tuple[int, int, int]:
+    """(S, blocks, slab bytes) of the split-K decode GEMM for x [M, K] @
+    W[N, K]^T; S == 0: the shape stays on the library GEMM."""
+    return tuple(_require_hip().decode_gemm_plan(int(M), int(N), int(K)))
+
+
+def linear_splitk(x, w, *, nan_fill: bool = False):
+    """F.linear(x, w) for decode rows as split-K partials: fp32 [S, M, N]
+    whose sum over dim 0 is x @ w^T, to be reduced by the consumer
+    (ops.rmsnorm_residual_partials).  x [M, K], w [N, K] bf16.  Shapes the
+    hand kernel does not plan (decode_gemm_plan S == 0: M > 32, N % 64,
+    K % 32, or too small to fill the chip) go through ops.lt_linear and
+    come back as one slice.  nan_fill pre-fills the slabs with NaN (tests:
+    every element must be written).  CPU: one fp32 slice."""
+    if not _on_gpu(x):
+        return torch_ref.linear_splitk(x, w)
+    hip = _require_hip()
+    M, K = x.shape
+    if hip.decode_gemm_plan(M, w.shape[0], K)[0] > 0:
+        return hip.decode_gemm_splitk(x.contiguous(), w.contiguous(),
+                                      bool(nan_fill))
+    return lt_linear(x, w).float().unsqueeze(0)
+
+
 _lt_ok = True
 
 
@@ -559,5 +595,5 @@ def gemm_bf16(a, b):
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
-    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "sample_token", "sample_filtered", "sample_slots", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
+    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

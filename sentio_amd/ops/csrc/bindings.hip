@@ -7,6 +7,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <limits>
 #include <tuple>
 
 #include "sentio_kernels.h"
@@ -510,6 +511,92 @@ void kv_store_fp8(torch::Tensor src_k, torch::Tensor src_v, torch::Tensor kc,
             "kv_store_fp8");
 }
 
+// Launch policy of the split-K decode GEMM: (S, blocks, slab bytes) for
+// x [M, K] @ W[N, K]^T.  S = 0 means no plan: the kernel does not take the
+// shape (M > 32, N not a multiple of its 64-column tile, K not a multiple
+// of its 32-deep k-step) or no legal S reaches 128 blocks within 8 MB of
+// slabs, and the caller keeps the library GEMM.  Blocks = (N / 64) * S
+// should land in 256..512, one to two 8-wave blocks per CU; among those a
+// slice K / S of whole 512-deep chunks (8 weight loads per wave in flight,
+// twice) beats whole 256-deep ones, and then the smallest S wins: fewer
+// slab bytes for the norm kernel to sum (measured on llama3-8b: S = 4 for
+// both wo and down; profiles/decode_gemm_splitk.md).  SENTIO_GEMM_SPLITK
+// overrides S for shapes the kernel takes, for probes and tests.
+std::tuple<int, long, long> decode_gemm_plan(long M, long N, long K) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, "decode_gemm_plan: empty shape");
+  if (M > 32 || N % 64 || K % 32) return {0, 0, 0};
+  const long tiles = N / 64;
+  auto slab_bytes = [&](long s) { return s * M * N * 4; };
+  if (const char* ov = std::getenv("SENTIO_GEMM_SPLITK")) {
+    const long s = atol(ov);
+    TORCH_CHECK(s >= 1 && s <= 65535 && K % (32 * s) == 0,
+                "SENTIO_GEMM_SPLITK='", ov, "' does not split K=", K,
+                " into slices that are multiples of 32");
+    return {(int)s, tiles * s, slab_bytes(s)};
+  }
+  long best = 0, best_pen = 0, best_depth = 0;
+  for (long s = 1; s <= K / 32; ++s) {
+    if (K % (32 * s) || slab_bytes(s) > (8L << 20)) continue;
+    const long blocks = tiles * s, slice = K / s;
+    if (blocks < 128) continue;
+    const long pen = blocks < 256 ? 256 - blocks
+                   : blocks > 512 ? blocks - 512 : 0;
+    const long depth = slice % 512 == 0 ? 2 : slice % 256 == 0 ? 1 : 0;
+    if (!best || pen < best_pen || (pen == best_pen && depth > best_depth)) {
+      best = s; best_pen = pen; best_depth = depth;
+    }
+  }
+  if (!best) return {0, 0, 0};
+  return {(int)best, tiles * best, slab_bytes(best)};
+}
+
+// Split-K partials of x [M, K] @ w[N, K]^T as fp32 [S, M, N]; S from
+// decode_gemm_plan.  nan_fill (tests) pre-fills the slabs with NaN so that
+// an element the kernel does not write stays visible.
+torch::Tensor decode_gemm_splitk(torch::Tensor x, torch::Tensor w,
+                                 bool nan_fill) {
+  check_bf16_cuda(x, "x");
+  check_bf16_cuda(w, "w");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1),
+              "x [M,K], w [N,K]");
+  const long M = x.size(0), K = x.size(1), N = w.size(0);
+  const int S = std::get<0>(decode_gemm_plan(M, N, K));
+  TORCH_CHECK(S > 0, "decode_gemm_splitk: no plan for M=", M, " N=", N,
+              " K=", K, " (use the library GEMM)");
+  auto opts = x.options().dtype(torch::kFloat);
+  auto part = nan_fill
+      ? torch::full({S, M, N}, std::numeric_limits<float>::quiet_NaN(), opts)
+      : torch::empty({S, M, N}, opts);
+  check_hip(sentio_decode_gemm_splitk(x.data_ptr(), w.data_ptr(),
+                                      part.data_ptr<float>(), (int)M, (int)K,
+                                      (int)N, S, stream()),
+            "decode_gemm_splitk");
+  return part;
+}
+
+std::vector<torch::Tensor> rmsnorm_residual_partials(torch::Tensor part,
+                                                     torch::Tensor res,
+                                                     torch::Tensor w,
+                                                     double eps) {
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat &&
+              part.is_contiguous() && part.dim() >= 2,
+              "part must be a contiguous f32 [S, ..., D] GPU tensor");
+  check_bf16_cuda(res, "res");
+  check_bf16_cuda(w, "w");
+  const int S = part.size(0);
+  const int D = part.size(-1);
+  TORCH_CHECK(S >= 1 && res.numel() * S == part.numel() && res.size(-1) == D &&
+              w.numel() == D, "part [S, rows, D], res [rows, D], w [D]");
+  const long rows = res.numel() / D;
+  auto y = torch::empty_like(res);
+  auto h = torch::empty_like(res);
+  check_hip(sentio_rmsnorm_residual_partials(
+                part.data_ptr<float>(), res.data_ptr(), w.data_ptr(),
+                y.data_ptr(), h.data_ptr(), S, rows, D, (float)eps, stream()),
+            "rmsnorm_residual_partials");
+  return {y, h};
+}
+
 torch::Tensor gemm_bf16(torch::Tensor a, torch::Tensor b) {
   check_bf16_cuda(a, "a");
   check_bf16_cuda(b, "b");
@@ -609,6 +696,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_fused_fp8", &decode_attn_fused_fp8);
   m.def("kv_store_fp8", &kv_store_fp8);
   m.def("decode_attn_plan", &decode_attn_plan);
+  m.def("decode_gemm_plan", &decode_gemm_plan);
+  m.def("decode_gemm_splitk", &decode_gemm_splitk);
+  m.def("rmsnorm_residual_partials", &rmsnorm_residual_partials);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("fuse_topk", &fuse_topk);

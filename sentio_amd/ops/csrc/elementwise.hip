@@ -97,6 +97,67 @@ __global__ void rmsnorm_residual_kernel(const bf16* __restrict__ x,
   }
 }
 
+// rmsnorm_residual over split-K partials: part [S, rows, D] fp32 are the
+// slabs of decode_gemm_splitk.  p = ((part[0] + part[1]) + part[2]) + ...
+// in increasing s, f = p + res (the residual is added last, so S = 1 is
+// rmsnorm_residual on an unrounded projection), h = bf16(f), and as in
+// rmsnorm_residual_kernel the sum of squares takes the unrounded f while y
+// is formed from the rounded h.  One block per row, one 16-byte piece of
+// every slab per thread and step: the S loads of a piece are independent.
+template <int VEC>   // 4: float4 pieces (D % 4 == 0); 1: scalar
+__global__ void rmsnorm_residual_partials_kernel(
+    const float* __restrict__ part, const bf16* __restrict__ res,
+    const bf16* __restrict__ w, bf16* __restrict__ y, bf16* __restrict__ h,
+    int S, long rows, int D, float eps) {
+  __shared__ float scratch[32];
+  const long row = blockIdx.x;
+  const long slab = rows * (long)D;
+  const float* pr = part + row * (long)D;
+  const bf16* rr = res + row * (long)D;
+  bf16* yr = y + row * (long)D;
+  bf16* hr = h + row * (long)D;
+
+  float ss = 0.f;
+  for (int d = threadIdx.x * VEC; d < D; d += blockDim.x * VEC) {
+    if (VEC == 4) {
+      f32x4 a = *reinterpret_cast<const f32x4*>(pr + d);
+#pragma unroll 4
+      for (int s = 1; s < S; ++s)
+        a += *reinterpret_cast<const f32x4*>(pr + s * slab + d);
+      bf16x4 b = *reinterpret_cast<const bf16x4*>(rr + d);
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float f = a[j] + bits2f(b[j]);
+        o[j] = f2bits(f);
+        ss += f * f;
+      }
+      *reinterpret_cast<bf16x4*>(hr + d) = o;
+    } else {
+      float a = pr[d];
+      for (int s = 1; s < S; ++s) a += pr[s * slab + d];
+      const float f = a + bf2f(rr[d]);
+      hr[d] = f2bf(f);
+      ss += f * f;
+    }
+  }
+  ss = block_sum(ss, scratch);
+  const float inv = rsqrtf(ss / (float)D + eps);
+  for (int d = threadIdx.x * VEC; d < D; d += blockDim.x * VEC) {
+    if (VEC == 4) {
+      bf16x4 v = *reinterpret_cast<const bf16x4*>(hr + d);
+      bf16x4 wv = *reinterpret_cast<const bf16x4*>(w + d);
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        o[j] = f2bits(bits2f(v[j]) * inv * bits2f(wv[j]));
+      *reinterpret_cast<bf16x4*>(yr + d) = o;
+    } else {
+      yr[d] = f2bf(bf2f(hr[d]) * inv * bf2f(w[d]));
+    }
+  }
+}
+
 // ---------------------------------------------------------------- swiglu
 // out = silu(gate) * up, flat N elements, grid-stride, bf16x8 vectorized.
 __global__ void swiglu_kernel(const bf16* __restrict__ gate,
@@ -363,6 +424,30 @@ hipError_t sentio_rmsnorm_residual(const void* x, const void* res, const void* w
     hipLaunchKernelGGL((rmsnorm_residual_kernel<1>), dim3((unsigned)rows), block,
                        0, stream, (const bf16*)x, (const bf16*)res,
                        (const bf16*)w, (bf16*)y, (bf16*)h, D, eps);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_rmsnorm_residual_partials(const float* part, const void* res,
+                                            const void* w, void* y, void* h,
+                                            int S, long rows, int D, float eps,
+                                            hipStream_t stream) {
+  if (S < 1 || rows < 1 || D < 1) return hipErrorInvalidValue;
+  // 32 decode rows read S slabs: a piece per thread keeps every load of a
+  // row in flight at once instead of 256 threads looping over it
+  const int vec = (D % 4 == 0) ? 4 : 1;
+  int threads = ((D / vec + WAVE - 1) / WAVE) * WAVE;
+  threads = threads > 1024 ? 1024 : threads;
+  if (vec == 4)
+    hipLaunchKernelGGL((rmsnorm_residual_partials_kernel<4>),
+                       dim3((unsigned)rows), dim3(threads), 0, stream, part,
+                       (const bf16*)res, (const bf16*)w, (bf16*)y, (bf16*)h, S,
+                       rows, D, eps);
+  else
+    hipLaunchKernelGGL((rmsnorm_residual_partials_kernel<1>),
+                       dim3((unsigned)rows), dim3(threads), 0, stream, part,
+                       (const bf16*)res, (const bf16*)w, (bf16*)y, (bf16*)h, S,
+                       rows, D, eps);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -247,7 +247,230 @@ __global__ void skinny_gemm_kernel(const bf16* __restrict__ x,
   }
 }
 
+// ------------------------------------------------- split-K decode GEMM
+// part[s, m, n] = sum over k in slice s of x[m, k] * W[n, k]: x [M<=32, K]
+// bf16, W [N, K] bf16 (TN), part fp32 [S, M, N].  For the projections whose
+// output width is the model dimension (wo, down): at N = 4096 a tiling of
+// the output alone gives 64-128 blocks, so half of the 256 CUs never
+// stream; a split over K puts every CU on the weight from the first
+// microsecond.  Each block writes only its own slab tile with plain
+// stores; the slabs are summed by the consumer (rmsnorm_residual_partials),
+// so there is no reduce launch and no inter-block communication.
+//
+// Grid (N/64, S), block 512 = 8 waves.  Wave w: column strip w & 3 (16
+// columns, W rows straight to MFMA A fragments as in skinny_gemm: D row =
+// n, col = m) and k-group kg = w >> 2.  The block walks its slice in chunks
+// of CK = 2 * UNR * 32 k-values; load u < UNR of a wave is k-step
+// (u & 1) + 2 * kg + 4 * (u >> 1) of the chunk, so loads 2j and 2j + 1
+// are the two 64-byte halves of the same 128-byte line of every row.
+// (With the halves in different waves and non-temporal loads every line
+// was fetched twice: 2.9 TB/s where this order reaches 4.5.)  Per chunk a
+// wave issues its x staging loads, then all UNR W loads, and only then
+// waits: x is an L2 hit and returns first, goes to LDS, and the MFMAs
+// consume the W registers in issue order under counted vmcnt waits while
+// the next chunk's loads are already in flight.
+//
+// x goes through LDS in full lines: [MT][CK] bf16, 16-byte piece p of row
+// m stored at piece p ^ (m & 15), which makes the 16-lane ds_read_b128
+// groups of a B-fragment read conflict-free without padding.  Pieces past
+// the slice end or in rows >= M are staged as zeros and W loads clamp to
+// the slice's last k-step, so a ragged last chunk needs no predicated
+// load and padded rows contribute nothing.
+//
+// Epilogue: k-group 1 parks its accumulators in LDS, group 0 adds them
+// (acc0 + acc1, in that order), and the [MT][64] fp32 tile is stored one
+// 256-byte row piece per 16 lanes.  Rows >= M are never stored.
+#define SK_BN 64
+#define SK_THREADS 512
+
+template <int MT, int UNR>   // padded M (16 or 32), k-steps per wave and chunk
+__launch_bounds__(SK_THREADS, 2)
+__global__ void decode_gemm_splitk_kernel(const bf16* __restrict__ x,
+                                          const bf16* __restrict__ w,
+                                          float* __restrict__ part,
+                                          int M, int K, int N, int kslice) {
+  constexpr int MTILES = MT / 16;
+  constexpr int CK = 2 * UNR * 32;           // k-values per chunk
+  constexpr int PPR = CK / 8;                // 16-byte pieces per x row
+  constexpr int NX = MT * PPR / SK_THREADS;  // staging pieces per thread
+  constexpr int RPI = SK_THREADS / PPR;      // x rows per staging pass
+  static_assert(NX >= 1 && MT * PPR % SK_THREADS == 0, "staging shape");
+  static_assert(MT * CK * 2 >= MT * SK_BN * 4, "epilogue tile fits");
+  // one LDS object: the x chunk, reused as the epilogue tile
+  __shared__ __attribute__((aligned(16))) char smem[MT * CK * 2];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid / WAVE;
+  const int strip = wid & 3;
+  const int kg = wid >> 2;
+  const int arow = lane & 15;         // n within the strip / m within a tile
+  const int q = lane >> 4;            // k octet of the fragment
+  const int tile = blockIdx.x;
+  const int slice = blockIdx.y;
+  const int k_begin = slice * kslice;
+  const int k_end = k_begin + kslice;
+
+  const short* xs_base = reinterpret_cast<const short*>(x);
+  const short* wrow = reinterpret_cast<const short*>(w) +
+      (long)(tile * SK_BN + strip * 16 + arow) * K + q * 8;
+
+  f32x4_t acc[MTILES];
+#pragma unroll
+  for (int mt = 0; mt < MTILES; ++mt) acc[mt] = f32x4_t{};
+
+  // x piece (m, p) of a staging pass: m = i * RPI + t with RPI a power of
+  // two <= 16, so the swizzle p ^ (m & 15) splits into a per-thread part
+  // and a compile-time part
+  const int xt = tid / PPR;
+  const int xp = tid % PPR;
+  // B-fragment read offsets of even and odd u: k-step ls(u) = (u & 1) +
+  // 2 * kg + 4 * (u >> 1), piece (4 * ls + q) ^ arow; the swizzle reaches
+  // bits 0-3 (q, parity of u, kg), so two bases and an immediate offset
+  // cover every u
+  const int rd_base[2] = {
+      arow * (CK * 2) + (((kg * 8 + q) ^ arow) * 16),
+      arow * (CK * 2) + (((4 + kg * 8 + q) ^ arow) * 16)};
+
+  // all loads of chunk c: x first (L2 hits, they return ahead of the W
+  // stream), then the wave's UNR W fragments.  Plain loads, not
+  // non-temporal: the two 64-byte halves of a W line are fetched by
+  // consecutive instructions (u, u + 1) of one wave, and the second must
+  // find the line the first brought in
+  struct Chunk { bf16x8 x[NX]; bool ok[NX]; bf16x8 w[UNR]; };
+  auto load_chunk = [&](int c, Chunk& d) {
+    const int kc0 = k_begin + c * CK;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const int m = i * RPI + xt;
+      const int k = kc0 + xp * 8;
+      d.ok[i] = m < M && k < k_end;
+      d.x[i] = *reinterpret_cast<const bf16x8*>(
+          xs_base + (long)(d.ok[i] ? m : 0) * K + (d.ok[i] ? k : k_begin));
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int k = kc0 + ((u & 1) + 2 * kg + 4 * (u >> 1)) * 32;
+      d.w[u] = *reinterpret_cast<const bf16x8*>(wrow + min(k, k_end - 32));
+    }
+    // keep every load of the chunk ahead of the first wait: left alone, the
+    // scheduler sinks each W load next to its MFMA behind a vmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto stage_x = [&](const Chunk& d) {
+    __syncthreads();                  // the previous chunk's reads are done
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      bf16x8 v = d.x[i];
+      if (!d.ok[i]) v = bf16x8{};
+      const int piece = (xp ^ xt) ^ ((i * RPI) & 15);   // p ^ (m & 15)
+      *reinterpret_cast<bf16x8*>(smem + (i * RPI + xt) * (CK * 2) +
+                                 piece * 16) = v;
+    }
+    __syncthreads();
+  };
+  auto mma_chunk = [&](const Chunk& d) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const bf16x8_t a = __builtin_bit_cast(bf16x8_t, d.w[u]);
+#pragma unroll
+      for (int mt = 0; mt < MTILES; ++mt) {
+        const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(
+            smem + rd_base[u & 1] + (u >> 1) * 256 + mt * 16 * (CK * 2));
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[mt],
+                                                          0, 0, 0);
+      }
+    }
+  };
+
+  // Software pipeline over the chunks with two register sets: the loads of
+  // chunk c + 1 are issued before the MFMAs of chunk c and waited for only
+  // when chunk c + 1 is staged, so a wave always has a chunk in flight.
+  // The loop is unrolled by two so that no set is ever copied (a copy waits
+  // for its loads) and no load sits under a condition (hipcc then waits
+  // vmcnt(0) at the join).
+  const int nchunks = (kslice + CK - 1) / CK;
+  Chunk A, B;
+  int c = 0;
+  load_chunk(0, A);
+  for (; c + 2 < nchunks; c += 2) {
+    stage_x(A);
+    load_chunk(c + 1, B);
+    mma_chunk(A);
+    stage_x(B);
+    load_chunk(c + 2, A);
+    mma_chunk(B);
+  }
+  stage_x(A);
+  if (c + 1 < nchunks) {
+    load_chunk(c + 1, B);
+    mma_chunk(A);
+    stage_x(B);
+    mma_chunk(B);
+  } else {
+    mma_chunk(A);
+  }
+
+  // D-frag: lane l reg r -> n = strip*16 + (l>>4)*4 + r, m = mt*16 + (l&15)
+  __syncthreads();                    // x chunk no longer needed
+  float* red = reinterpret_cast<float*>(smem);        // [MT][SK_BN]
+  if (kg == 1) {
+#pragma unroll
+    for (int mt = 0; mt < MTILES; ++mt)
+      *reinterpret_cast<f32x4_t*>(red + (mt * 16 + arow) * SK_BN +
+                                  strip * 16 + q * 4) = acc[mt];
+  }
+  __syncthreads();
+  if (kg == 0) {
+#pragma unroll
+    for (int mt = 0; mt < MTILES; ++mt) {
+      f32x4_t* p = reinterpret_cast<f32x4_t*>(red + (mt * 16 + arow) * SK_BN +
+                                              strip * 16 + q * 4);
+      *p = acc[mt] + *p;
+    }
+  }
+  __syncthreads();
+  if (tid < MT * (SK_BN / 4)) {
+    const int row = tid / (SK_BN / 4);
+    const int c4 = tid % (SK_BN / 4);
+    if (row < M)
+      *reinterpret_cast<f32x4_t*>(part + ((long)slice * M + row) * N +
+                                  tile * SK_BN + c4 * 4) =
+          *reinterpret_cast<const f32x4_t*>(red + row * SK_BN + c4 * 4);
+  }
+}
+
+template <int MT, int UNR>
+static void launch_splitk(const void* x, const void* w, float* part, int M,
+                          int K, int N, int S, hipStream_t stream) {
+  hipLaunchKernelGGL((decode_gemm_splitk_kernel<MT, UNR>),
+                     dim3(N / SK_BN, S), dim3(SK_THREADS), 0, stream,
+                     (const bf16*)x, (const bf16*)w, part, M, K, N, K / S);
+}
+
 extern "C" {
+
+hipError_t sentio_decode_gemm_splitk(const void* x, const void* w, float* part,
+                                     int M, int K, int N, int S,
+                                     hipStream_t stream) {
+  if (M < 1 || M > 32 || S < 1 || S > 65535 || K < 32 || N < SK_BN ||
+      (N % SK_BN) || (K % (32 * S)))
+    return hipErrorInvalidValue;
+  // 8 k-steps per wave and chunk when the slice is whole 512-deep chunks,
+  // else 4 (256-deep; a ragged last chunk re-reads the slice's final k-step
+  // against zeros).  16 measured slower at every S: 228 VGPRs leave one
+  // block per CU
+  const bool deep = (K / S) % 512 == 0;
+  if (M <= 16) {
+    if (deep) launch_splitk<16, 8>(x, w, part, M, K, N, S, stream);
+    else launch_splitk<16, 4>(x, w, part, M, K, N, S, stream);
+  } else {
+    if (deep) launch_splitk<32, 8>(x, w, part, M, K, N, S, stream);
+    else launch_splitk<32, 4>(x, w, part, M, K, N, S, stream);
+  }
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 hipError_t sentio_skinny_gemm(const void* x, const void* w, void* out, int M,
                               int K, int N, hipStream_t stream) {

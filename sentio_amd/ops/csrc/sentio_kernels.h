@@ -16,6 +16,12 @@ hipError_t sentio_rmsnorm(const void* x, const void* w, void* y, long rows,
 hipError_t sentio_rmsnorm_residual(const void* x, const void* res,
                                    const void* w, void* y, void* h, long rows,
                                    int D, float eps, hipStream_t stream);
+// part is fp32 [S, rows, D], slabs summed in increasing s; S sits BEFORE
+// rows and D; writes y and h like sentio_rmsnorm_residual
+hipError_t sentio_rmsnorm_residual_partials(const float* part, const void* res,
+                                            const void* w, void* y, void* h,
+                                            int S, long rows, int D, float eps,
+                                            hipStream_t stream);
 hipError_t sentio_swiglu(const void* gate, const void* up, void* out, long n,
                          hipStream_t stream);
 // F is the OUTPUT width (half the packed [gate | up] row)
@@ -131,6 +137,12 @@ hipError_t sentio_gemm_bf16(const void* A, const void* B, void* C, int M,
 // w is [N, K] row-major (TN); dims are (M, K, N) — NOT (M, N, K)
 hipError_t sentio_skinny_gemm(const void* x, const void* w, void* out, int M,
                               int K, int N, hipStream_t stream);
+// split-K partials: w is [N, K] row-major (TN), part is fp32 [S, M, N];
+// dims are (M, K, N, S) like skinny_gemm.  hipErrorInvalidValue unless
+// 1 <= M <= 32, N % 64 == 0 and K % (32 * S) == 0
+hipError_t sentio_decode_gemm_splitk(const void* x, const void* w, float* part,
+                                     int M, int K, int N, int S,
+                                     hipStream_t stream);
 // w is [N, K] row-major (TN) like skinny_gemm, but dims are (M, N, K);
 // returns 0 on success, not a hipError_t
 int sentio_lt_gemm_tn(const void* x, const void* w, void* out, int M, int N,

@@ -31,6 +31,25 @@ def rmsnorm_residual(
     return y, h.to(x.dtype)
 
 
+def linear_splitk(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Split-K partials of F.linear(x, w) as fp32 [S, M, N]; the reference
+    has one slice."""
+    return torch.nn.functional.linear(x.float(), w.float()).unsqueeze(0)
+
+
+def rmsnorm_residual_partials(
+    part: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor,
+    eps: float = 1e-5
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """rmsnorm_residual on the sum of fp32 partials [S, ..., D] over dim 0:
+    h = sum_s part[s] + residual;  y = rmsnorm(h).  Returns (y, h) in the
+    residual's dtype."""
+    h = part.float().sum(dim=0).reshape(residual.shape) + residual.float()
+    rms = h.pow(2).mean(dim=-1, keepdim=True).add(eps).rsqrt()
+    y = (h * rms * weight.float()).to(residual.dtype)
+    return y, h.to(residual.dtype)
+
+
 def rope_tables(
     max_seq: int, head_dim: int, base: float = 500000.0, device: str = "cpu"
 ) -> tuple[torch.Tensor, torch.Tensor]:
