@@ -246,6 +246,20 @@ class Transformer:
         # and a shape ops.decode_gemm_plan accepts.  SENTIO_DECODE_GEMM=lt
         # keeps the library path; wo / down route only that projection.
         self.splitk_wo, self.splitk_down = self._plan_decode_gemm()
+        # Multi-token head prep (generator / verifier prefill, prefix and
+        # suffix forwards, encoder, reranker), fixed for the model's
+        # lifetime like the two choices above: one ops.prefill_qkv_prep
+        # launch splits the QKV projection, applies RoPE and writes K/V
+        # into the cache, where the legacy sequence ran three slice copies,
+        # two rope launches and two indexed writes per layer.  It needs the
+        # GPU, bf16 and a head dim that is a multiple of 8.
+        # SENTIO_PREFILL_PREP=legacy keeps the old sequence.
+        self.prefill_fused = (
+            os.environ.get("SENTIO_PREFILL_PREP", "auto") != "legacy"
+            and str(self.device).startswith("cuda")
+            and self.dtype == torch.bfloat16
+            and ops.hip_available()
+            and cfg.head_dim % 8 == 0)
 
     def _plan_decode_gemm(self) -> tuple[bool, bool]:
         mode = os.environ.get("SENTIO_DECODE_GEMM", "auto")
@@ -260,15 +274,54 @@ class Transformer:
         return wo and mode != "down", down and mode != "wo"
 
     # ----- core blocks -----
-    def _attn(self, x: torch.Tensor, layer: dict, pos: torch.Tensor,
+    def _prep_fused(self, pos: torch.Tensor | None, cache: KVCache | None,
+                    S: int) -> bool:
+        """Whether a forward_hidden call takes ops.prefill_qkv_prep: the
+        construction-time choice, positions q_off + arange(S) (no explicit
+        pos), and with a cache a causal multi-token forward into bf16 rows
+        (S == 1 keeps the decode-attention branch, an FP8 cache its
+        error)."""
+        if not self.prefill_fused or pos is not None:
+            return False
+        if cache is None:
+            return True
+        return (S > 1 and self.cfg.causal and not cache.fp8
+                and cache.k[0].dtype == torch.bfloat16
+                and cache.k[0].is_cuda)
+
+    def _attn_fused(self, qkv: torch.Tensor, cache: KVCache | None,
+                    layer_idx: int, kv_lens: torch.Tensor | None,
+                    q_off: int) -> torch.Tensor:
+        """Head prep in one launch, then attention: against the cache rows
+        just written (kv_lens: absolute lengths, set by forward_hidden), or
+        over the contiguous k / v without a cache."""
+        H, Hkv = self.h_local, self.hkv_local
+        if cache is not None:
+            kc, vc = cache.k[layer_idx], cache.v[layer_idx]
+            q = ops.prefill_qkv_prep(qkv, self.rope_cos, self.rope_sin, q_off,
+                                     H, Hkv, kc, vc)
+            return ops.attention_cache(q, kc, vc, kv_lens, q_off, self.scale)
+        q, k, v = ops.prefill_qkv_prep(qkv, self.rope_cos, self.rope_sin,
+                                       q_off, H, Hkv)
+        return ops.attention(q, k, v, causal=self.cfg.causal,
+                             scale=self.scale, kv_lens=kv_lens)
+
+    def _attn(self, x: torch.Tensor, layer: dict, pos: torch.Tensor | None,
               cache: KVCache | None, layer_idx: int,
               kv_lens: torch.Tensor | None, q_off: int = 0) -> torch.Tensor:
+        """pos None: the fused head prep (forward_hidden decided, see
+        _prep_fused); otherwise the rope / indexed-write sequence."""
         cfg = self.cfg
         B, S, d = x.shape
         hd = cfg.head_dim
         H, Hkv = self.h_local, self.hkv_local
         qkv = torch.nn.functional.linear(x.view(B * S, d), layer["wqkv"])
         qkv = qkv.view(B, S, -1)
+        if pos is None:
+            out = self._attn_fused(qkv, cache, layer_idx, kv_lens, q_off)
+            out = linear_row_parallel(out.reshape(B * S, H * hd), layer["wo"],
+                                      self.tp)
+            return out.view(B, S, d)
         q_end = H * hd
         k_end = q_end + Hkv * hd
         q = qkv[..., :q_end].reshape(B, S, H, hd)
@@ -344,10 +397,17 @@ class Transformer:
         """tokens: [B, S] int64 → hidden [B, S, dim] (after final norm).
         kv_lens: right-padding valid lengths for non-causal batches.
         Residual adds are fused into the next block's RMSNorm
-        (ops.rmsnorm_residual) — one kernel instead of add + norm."""
+        (ops.rmsnorm_residual) — one kernel instead of add + norm.
+        pos None: token (b, s) sits at position q_off + s; on the fused
+        head-prep route (_prep_fused) no position tensor is built at all."""
         B, S = tokens.shape
-        if pos is None:
-            pos = torch.arange(S, device=tokens.device).unsqueeze(0).expand(B, S)
+        if self._prep_fused(pos, cache, S):
+            if cache is not None and kv_lens is None:
+                kv_lens = torch.full((B,), q_off + S, dtype=torch.int32,
+                                     device=tokens.device)
+        elif pos is None:
+            pos = torch.arange(q_off, q_off + S, device=tokens.device
+                               ).unsqueeze(0).expand(B, S)
         x = self.w.tok_emb[tokens.reshape(-1)].view(B, S, self.cfg.dim)
         eps = self.cfg.norm_eps
         layers = self.w.layers
@@ -487,11 +547,10 @@ class Transformer:
         last-real-position logits; suffix_lens: per-row true suffix lengths
         for right-padded suffix batches."""
         B, S = suffix_tokens.shape
-        pos = (prefix_len + torch.arange(S, device=suffix_tokens.device)
-               ).unsqueeze(0).expand(B, S)
         lens_abs = (None if suffix_lens is None
                     else (suffix_lens.to(torch.int32) + prefix_len))
-        hidden = self.forward_hidden(suffix_tokens, pos=pos, cache=cache,
+        # positions prefix_len + s follow from q_off
+        hidden = self.forward_hidden(suffix_tokens, cache=cache,
                                      q_off=prefix_len, kv_lens=lens_abs)
         if lens_abs is None:
             cache.seq_lens[:] = prefix_len + S

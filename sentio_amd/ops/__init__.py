@@ -67,14 +67,19 @@ def rmsnorm_residual(x, residual, weight, eps: float = 1e-5):
     return torch_ref.rmsnorm_residual(x, residual, weight, eps)
 
 
-def rmsnorm_residual_partials(part, residual, weight, eps: float = 1e-5):
+def rmsnorm_residual_partials(part, residual, weight, eps: float = 1e-5, *,
+                              reread: bool = False):
     """ops.rmsnorm_residual with the projection given as split-K partials:
     part fp32 [S, rows, D] (ops.linear_splitk), summed in increasing s, plus
     residual [..., D] → (y, h) shaped like residual.  The sum never rounds
-    to bf16 before the residual add."""
+    to bf16 before the residual add.  On the GPU rows of at most 8192
+    elements keep h in registers between the two passes; reread=True takes
+    the kernel that loads h back at any row length (tests and probes; the
+    outputs are bit-identical)."""
     if _on_gpu(part):
         y, h = _require_hip().rmsnorm_residual_partials(
-            part.contiguous(), residual.contiguous(), weight.contiguous(), eps)
+            part.contiguous(), residual.contiguous(), weight.contiguous(), eps,
+            bool(reread))
         return y, h
     return torch_ref.rmsnorm_residual_partials(part, residual, weight, eps)
 
@@ -95,6 +100,76 @@ def decode_qkv_prep(qkv, k_cache, v_cache, cos, sin, seq_lens):
         return _require_hip().decode_qkv_prep(
             qkv.contiguous(), k_cache, v_cache, cos, sin, seq_lens)
     return torch_ref.decode_qkv_prep(qkv, k_cache, v_cache, cos, sin, seq_lens)
+
+
+def prefill_qkv_prep(qkv, cos, sin, pos0: int, n_heads: int, n_kv_heads: int,
+                     k_cache=None, v_cache=None):
+    """Fused prefill head prep: split the raw projection qkv
+    [B, S, (H+2*Hkv)*D], RoPE q and k (token (b, s) sits at position
+    pos0 + s) and put k / v in their final place, in one launch.
+
+    With caches [Bc, Hkv, Smax, D]: RoPE(k) and v are written to rows
+    pos0 .. pos0+S-1 of batch rows 0 .. B-1 (every row of a right-padded
+    batch; nothing else is touched) and q [B, S, H, D] is returned.
+    Without: returns (q, k, v), k and v contiguous [B, S, Hkv, D].
+
+    Nothing is converted or copied: qkv must be contiguous, the tables
+    contiguous float32 [rows, D/2], all on one device, D % 8 == 0,
+    Bc >= B, 0 <= pos0, pos0 + S <= rows and pos0 + S <= Smax — anything
+    else raises ValueError before a launch."""
+    if not isinstance(qkv, torch.Tensor) or qkv.dim() != 3 \
+            or qkv.numel() == 0:
+        raise ValueError("qkv must be a non-empty [B, S, (H+2*Hkv)*D] tensor")
+    if not qkv.is_contiguous():
+        raise ValueError("qkv must be contiguous")
+    B, S, W = qkv.shape
+    H, Hkv, pos0 = int(n_heads), int(n_kv_heads), int(pos0)
+    if H < 1 or Hkv < 1 or W % (H + 2 * Hkv):
+        raise ValueError(f"qkv width {W} is not ({H}+2*{Hkv})*D")
+    D = W // (H + 2 * Hkv)
+    if D % 8:
+        raise ValueError(f"head dim must be a multiple of 8, got {D}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 \
+                or t.dim() != 2 or t.shape[1] != D // 2 \
+                or not t.is_contiguous() or t.device != qkv.device:
+            raise ValueError(f"{name} must be a contiguous float32 "
+                             f"[rows, {D // 2}] tensor on {qkv.device}")
+    if sin.shape[0] != cos.shape[0]:
+        raise ValueError("cos and sin differ in rows")
+    if pos0 < 0:
+        raise ValueError(f"pos0 must be >= 0, got {pos0}")
+    if pos0 + S > cos.shape[0]:
+        raise ValueError(f"positions {pos0} .. {pos0 + S - 1} exceed the "
+                         f"{cos.shape[0]} rope table rows")
+    if (k_cache is None) != (v_cache is None):
+        raise ValueError("give both caches or neither")
+    if k_cache is not None:
+        for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 \
+                    or t.dtype != qkv.dtype or not t.is_contiguous() \
+                    or t.device != qkv.device:
+                raise ValueError(f"{name} must be a contiguous {qkv.dtype} "
+                                 f"[Bc, Hkv, Smax, D] tensor on {qkv.device}")
+        if v_cache.shape != k_cache.shape or k_cache.shape[1] != Hkv \
+                or k_cache.shape[3] != D:
+            raise ValueError(f"caches must both be [Bc, {Hkv}, Smax, {D}], "
+                             f"got {tuple(k_cache.shape)} / "
+                             f"{tuple(v_cache.shape)}")
+        if k_cache.shape[0] < B:
+            raise ValueError(f"cache has {k_cache.shape[0]} batch rows "
+                             f"for {B}")
+        if pos0 + S > k_cache.shape[2]:
+            raise ValueError(f"positions {pos0} .. {pos0 + S - 1} exceed the "
+                             f"cache's {k_cache.shape[2]} rows")
+    if _on_gpu(qkv):
+        if qkv.dtype != torch.bfloat16:
+            raise ValueError(f"qkv must be bf16 on the GPU, got {qkv.dtype}")
+        out = _require_hip().prefill_qkv_prep(qkv, cos, sin, pos0, H, Hkv,
+                                              k_cache, v_cache)
+        return out[0] if k_cache is not None else tuple(out)
+    return torch_ref.prefill_qkv_prep(qkv, cos, sin, pos0, H, Hkv, k_cache,
+                                      v_cache)
 
 
 def swiglu(gate, up):
@@ -593,7 +668,7 @@ def gemm_bf16(a, b):
 
 
 __all__ = [
-    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
+    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -112,6 +112,79 @@ torch::Tensor decode_qkv_prep(torch::Tensor qkv, torch::Tensor kc,
   return q_out;
 }
 
+void check_caches(const torch::Tensor& kc, const torch::Tensor& vc);
+
+// Prefill head prep in one launch: split the raw QKV projection
+// [B, S, (H+2*Hkv)*D], RoPE q and k at positions pos0 + s, and write k / v
+// into the caches' rows pos0 .. pos0+S-1 (returns {q}) or, without caches,
+// into new contiguous tensors (returns {q, k, v}).  Everything is checked
+// before the launch; nothing synchronises, so it can be graph-captured.
+std::vector<torch::Tensor> prefill_qkv_prep(
+    torch::Tensor qkv, torch::Tensor cosT, torch::Tensor sinT, int64_t pos0,
+    int64_t H, int64_t Hkv, c10::optional<torch::Tensor> kc,
+    c10::optional<torch::Tensor> vc) {
+  check_bf16_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, S, (H+2*Hkv)*D]");
+  TORCH_CHECK(kc.has_value() == vc.has_value(),
+              "give both caches or neither");
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(B > 0 && S > 0, "qkv must be non-empty");
+  TORCH_CHECK(H > 0 && Hkv > 0 && W % (H + 2 * Hkv) == 0,
+              "qkv width ", W, " is not (", H, "+2*", Hkv, ")*D");
+  const int64_t D = W / (H + 2 * Hkv);
+  TORCH_CHECK(D >= 8 && D % 8 == 0,
+              "head dim must be a multiple of 8, got ", D);
+  TORCH_CHECK(B * S <= std::numeric_limits<int>::max() &&
+              W <= std::numeric_limits<int>::max(), "qkv too large");
+  auto aligned = [](const torch::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(aligned(qkv), "qkv must be 16-byte aligned");
+  for (const auto* t : {&cosT, &sinT}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() &&
+                t->scalar_type() == torch::kFloat && t->is_contiguous() &&
+                t->dim() == 2 && t->size(1) == D / 2 && aligned(*t),
+                "rope tables must be contiguous 16-byte aligned f32 "
+                "[rows, D/2] on qkv's device");
+  }
+  TORCH_CHECK(sinT.size(0) == cosT.size(0), "rope tables differ in rows");
+  const int64_t rows = cosT.size(0);
+  TORCH_CHECK(rows <= std::numeric_limits<int>::max(), "rope tables too long");
+  TORCH_CHECK(pos0 >= 0, "pos0 must be >= 0, got ", pos0);
+  TORCH_CHECK(pos0 + S <= rows, "positions ", pos0, " .. ", pos0 + S - 1,
+              " exceed the ", rows, " rope table rows");
+  auto q = torch::empty({B, S, H, D}, qkv.options());
+  int64_t Bc = 0, Smax = 0;
+  torch::Tensor k, v;
+  if (kc.has_value()) {
+    check_caches(*kc, *vc);
+    TORCH_CHECK(kc->device() == qkv.device() && vc->device() == qkv.device(),
+                "caches and qkv on different devices");
+    TORCH_CHECK(kc->size(1) == Hkv && kc->size(3) == D,
+                "caches must be [Bc, ", Hkv, ", Smax, ", D, "]");
+    TORCH_CHECK(aligned(*kc) && aligned(*vc),
+                "caches must be 16-byte aligned");
+    Bc = kc->size(0);
+    Smax = kc->size(2);
+    TORCH_CHECK(Bc >= B, "cache has ", Bc, " batch rows for ", B);
+    TORCH_CHECK(Smax > 0 && Smax <= std::numeric_limits<int>::max() &&
+                pos0 + S <= Smax, "positions ", pos0, " .. ", pos0 + S - 1,
+                " exceed the cache's ", Smax, " rows");
+    k = *kc;
+    v = *vc;
+  } else {
+    k = torch::empty({B, S, Hkv, D}, qkv.options());
+    v = torch::empty({B, S, Hkv, D}, qkv.options());
+  }
+  check_hip(sentio_prefill_qkv_prep(
+                qkv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                cosT.data_ptr<float>(), sinT.data_ptr<float>(), (int)B, (int)S,
+                (int)H, (int)Hkv, (int)D, (int)Bc, (int)Smax, (int)pos0,
+                (int)rows, stream()), "prefill_qkv_prep");
+  if (kc.has_value()) return {q};
+  return {q, k, v};
+}
+
 torch::Tensor softmax_lastdim(torch::Tensor x) {
   check_bf16_cuda(x, "x");
   const int D = x.size(-1);
@@ -574,10 +647,12 @@ torch::Tensor decode_gemm_splitk(torch::Tensor x, torch::Tensor w,
   return part;
 }
 
+// reread: take the kernel that loads h back from memory at any row length
+// (tests compare the register path against it)
 std::vector<torch::Tensor> rmsnorm_residual_partials(torch::Tensor part,
                                                      torch::Tensor res,
                                                      torch::Tensor w,
-                                                     double eps) {
+                                                     double eps, bool reread) {
   TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat &&
               part.is_contiguous() && part.dim() >= 2,
               "part must be a contiguous f32 [S, ..., D] GPU tensor");
@@ -592,7 +667,8 @@ std::vector<torch::Tensor> rmsnorm_residual_partials(torch::Tensor part,
   auto h = torch::empty_like(res);
   check_hip(sentio_rmsnorm_residual_partials(
                 part.data_ptr<float>(), res.data_ptr(), w.data_ptr(),
-                y.data_ptr(), h.data_ptr(), S, rows, D, (float)eps, stream()),
+                y.data_ptr(), h.data_ptr(), S, rows, D, (float)eps,
+                reread ? 1 : 0, stream()),
             "rmsnorm_residual_partials");
   return {y, h};
 }
@@ -681,6 +757,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_packed", &swiglu_packed);
   m.def("rope_apply", &rope_apply);
   m.def("decode_qkv_prep", &decode_qkv_prep);
+  m.def("prefill_qkv_prep", &prefill_qkv_prep);
   m.def("softmax_lastdim", &softmax_lastdim);
   m.def("mean_pool_l2norm", &mean_pool_l2norm);
   m.def("sample_token", &sample_token);
@@ -698,7 +775,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_plan", &decode_attn_plan);
   m.def("decode_gemm_plan", &decode_gemm_plan);
   m.def("decode_gemm_splitk", &decode_gemm_splitk);
-  m.def("rmsnorm_residual_partials", &rmsnorm_residual_partials);
+  m.def("rmsnorm_residual_partials", &rmsnorm_residual_partials,
+        py::arg("part"), py::arg("res"), py::arg("w"), py::arg("eps"),
+        py::arg("reread") = false);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("fuse_topk", &fuse_topk);

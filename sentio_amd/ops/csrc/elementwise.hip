@@ -104,7 +104,13 @@ __global__ void rmsnorm_residual_kernel(const bf16* __restrict__ x,
 // rmsnorm_residual_kernel the sum of squares takes the unrounded f while y
 // is formed from the rounded h.  One block per row, one 16-byte piece of
 // every slab per thread and step: the S loads of a piece are independent.
-template <int VEC>   // 4: float4 pieces (D % 4 == 0); 1: scalar
+// STEPS > 0 (VEC == 4, a row of at most STEPS pieces per thread): the
+// rounded h pieces and the norm weight stay in registers across the
+// reduction, so y is formed without loading h back from global memory
+// (decode rows are latency-bound: one round trip less).  STEPS == 0
+// re-reads h in a loop (any row length).  Same values in the same order
+// either way: outputs are bit-identical.
+template <int VEC, int STEPS>   // VEC 4: float4 pieces (D % 4 == 0); 1: scalar
 __global__ void rmsnorm_residual_partials_kernel(
     const float* __restrict__ part, const bf16* __restrict__ res,
     const bf16* __restrict__ w, bf16* __restrict__ y, bf16* __restrict__ h,
@@ -116,6 +122,45 @@ __global__ void rmsnorm_residual_partials_kernel(
   const bf16* rr = res + row * (long)D;
   bf16* yr = y + row * (long)D;
   bf16* hr = h + row * (long)D;
+
+  if constexpr (STEPS > 0) {
+    static_assert(STEPS == 0 || VEC == 4, "register path is float4 only");
+    bf16x4 hv[STEPS], wv[STEPS];
+    float ss = 0.f;
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+      const int d = (threadIdx.x + st * blockDim.x) * 4;
+      if (d < D) {
+        f32x4 a = *reinterpret_cast<const f32x4*>(pr + d);
+#pragma unroll 4
+        for (int s = 1; s < S; ++s)
+          a += *reinterpret_cast<const f32x4*>(pr + s * slab + d);
+        bf16x4 b = *reinterpret_cast<const bf16x4*>(rr + d);
+        wv[st] = *reinterpret_cast<const bf16x4*>(w + d);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float f = a[j] + bits2f(b[j]);
+          hv[st][j] = f2bits(f);
+          ss += f * f;
+        }
+        *reinterpret_cast<bf16x4*>(hr + d) = hv[st];
+      }
+    }
+    ss = block_sum(ss, scratch);
+    const float inv = rsqrtf(ss / (float)D + eps);
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+      const int d = (threadIdx.x + st * blockDim.x) * 4;
+      if (d < D) {
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = f2bits(bits2f(hv[st][j]) * inv * bits2f(wv[st][j]));
+        *reinterpret_cast<bf16x4*>(yr + d) = o;
+      }
+    }
+    return;
+  }
 
   float ss = 0.f;
   for (int d = threadIdx.x * VEC; d < D; d += blockDim.x * VEC) {
@@ -212,6 +257,20 @@ __global__ void swiglu_tail_kernel(const bf16* __restrict__ gate,
 }
 
 // ---------------------------------------------------------------- rope
+// The rotation of one pair, shared by rope_kernel and
+// prefill_qkv_prep_kernel so that both round identically (one expression,
+// one contraction).
+__device__ __forceinline__ void rope_rotate(float x0, float x1, float c,
+                                            float sn, bf16& y0, bf16& y1) {
+  y0 = f2bf(x0 * c - x1 * sn);
+  y1 = f2bf(x0 * sn + x1 * c);
+}
+__device__ __forceinline__ short bf2bits(bf16 v) {
+  short s;
+  __builtin_memcpy(&s, &v, sizeof(s));
+  return s;
+}
+
 // x [B, S, H, D] bf16 in-place-able; cos/sin [maxS, D/2] f32; pos [B, S] i32.
 // Each thread rotates one (pair) element: total B*S*H*D/2 pairs.
 __global__ void rope_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
@@ -232,8 +291,73 @@ __global__ void rope_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
     long base = rest * (long)D + 2 * p;
     float x0 = bf2f(x[base]);
     float x1 = bf2f(x[base + 1]);
-    y[base] = f2bf(x0 * c - x1 * sn);
-    y[base + 1] = f2bf(x0 * sn + x1 * c);
+    rope_rotate(x0, x1, c, sn, y[base], y[base + 1]);
+  }
+}
+
+// ------------------------------------------------------ prefill qkv prep
+// The prefill counterpart of decode_qkv_prep_kernel: reads the raw QKV
+// projection [B, S, (H+2*Hkv)*D] once and writes every value once into its
+// final place — RoPE(q) to q_out [B, S, H, D], RoPE(k) and v either into
+// the KV caches [Bc, Hkv, Smax, D] at rows pos0 .. pos0+S-1 (CACHE) or to
+// contiguous [B, S, Hkv, D] tensors.  Token (b, s) sits at position
+// pos0 + s.  It replaces three strided slice copies, two rope launches
+// and two indexed cache writes per layer.
+// One 16-byte piece (8 bf16 = 4 pairs) per thread and step; a block walks
+// the pieces of `tpb` consecutive tokens of one batch row, indexed by
+// (token, piece within the token's row) and advanced without a division.
+// The host validated every bound (sentio_prefill_qkv_prep).
+#define PREP_THREADS 256
+template <bool CACHE>
+__launch_bounds__(PREP_THREADS)
+__global__ void prefill_qkv_prep_kernel(
+    const bf16* __restrict__ qkv, bf16* __restrict__ q_out,
+    bf16* __restrict__ k_out, bf16* __restrict__ v_out,
+    const float* __restrict__ cosT, const float* __restrict__ sinT,
+    int S, int H, int Hkv, int D, int Smax, int pos0, int tpb, int nsb) {
+  const int ph = D >> 3;                 // pieces per head
+  const int P = (H + 2 * Hkv) * ph;      // pieces per token row
+  const int half = D >> 1;
+  const int b = blockIdx.x / nsb;
+  const int s0 = (blockIdx.x - b * nsb) * tpb;
+  const int nt = min(tpb, S - s0);       // tokens of this block
+  const int step_t = PREP_THREADS / P, step_p = PREP_THREADS % P;
+  int t = threadIdx.x / P;
+  int p = threadIdx.x - t * P;
+  while (t < nt) {
+    const int s = s0 + t;
+    const long tok = (long)b * S + s;
+    const int pos = pos0 + s;
+    const int hd = p / ph;               // head within the packed row
+    const int d = (p - hd * ph) * 8;     // first element within the head
+    bf16x8 x = *reinterpret_cast<const bf16x8*>(qkv + (tok * P + p) * 8);
+    bf16* dst;
+    if (hd < H) {
+      dst = q_out + (tok * H + hd) * D + d;
+    } else {
+      const bool is_k = hd < H + Hkv;
+      const int hk = hd - H - (is_k ? 0 : Hkv);
+      bf16* base = is_k ? k_out : v_out;
+      dst = CACHE ? base + ((((long)b * Hkv + hk) * Smax + pos) * D + d)
+                  : base + ((tok * Hkv + hk) * D + d);
+    }
+    if (hd < H + Hkv) {                  // q or k: rotate the 4 pairs
+      const long ti = (long)pos * half + (d >> 1);
+      const f32x4 c = *reinterpret_cast<const f32x4*>(cosT + ti);
+      const f32x4 sn = *reinterpret_cast<const f32x4*>(sinT + ti);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bf16 y0, y1;
+        rope_rotate(bits2f(x[2 * j]), bits2f(x[2 * j + 1]), c[j], sn[j], y0,
+                    y1);
+        x[2 * j] = bf2bits(y0);
+        x[2 * j + 1] = bf2bits(y1);
+      }
+    }
+    *reinterpret_cast<bf16x8*>(dst) = x;
+    t += step_t;
+    p += step_p;
+    if (p >= P) { p -= P; ++t; }
   }
 }
 
@@ -431,23 +555,25 @@ hipError_t sentio_rmsnorm_residual(const void* x, const void* res, const void* w
 hipError_t sentio_rmsnorm_residual_partials(const float* part, const void* res,
                                             const void* w, void* y, void* h,
                                             int S, long rows, int D, float eps,
-                                            hipStream_t stream) {
+                                            int reread, hipStream_t stream) {
   if (S < 1 || rows < 1 || D < 1) return hipErrorInvalidValue;
   // 32 decode rows read S slabs: a piece per thread keeps every load of a
   // row in flight at once instead of 256 threads looping over it
   const int vec = (D % 4 == 0) ? 4 : 1;
   int threads = ((D / vec + WAVE - 1) / WAVE) * WAVE;
   threads = threads > 1024 ? 1024 : threads;
-  if (vec == 4)
-    hipLaunchKernelGGL((rmsnorm_residual_partials_kernel<4>),
-                       dim3((unsigned)rows), dim3(threads), 0, stream, part,
-                       (const bf16*)res, (const bf16*)w, (bf16*)y, (bf16*)h, S,
-                       rows, D, eps);
-  else
-    hipLaunchKernelGGL((rmsnorm_residual_partials_kernel<1>),
-                       dim3((unsigned)rows), dim3(threads), 0, stream, part,
-                       (const bf16*)res, (const bf16*)w, (bf16*)y, (bf16*)h, S,
-                       rows, D, eps);
+  // rows of one or two float4 pieces per thread keep h in registers
+  const int steps = (vec != 4 || reread) ? 0 : (D / 4 + threads - 1) / threads;
+#define RP_LAUNCH(VEC, STEPS)                                                \
+  hipLaunchKernelGGL((rmsnorm_residual_partials_kernel<VEC, STEPS>),         \
+                     dim3((unsigned)rows), dim3(threads), 0, stream, part,   \
+                     (const bf16*)res, (const bf16*)w, (bf16*)y, (bf16*)h, S, \
+                     rows, D, eps)
+  if (vec == 1) RP_LAUNCH(1, 0);
+  else if (steps == 1) RP_LAUNCH(4, 1);
+  else if (steps == 2) RP_LAUNCH(4, 2);
+  else RP_LAUNCH(4, 0);
+#undef RP_LAUNCH
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }
@@ -504,6 +630,50 @@ hipError_t sentio_decode_qkv_prep(const void* qkv, void* q_out, void* kc,
   hipLaunchKernelGGL(decode_qkv_prep_kernel, dim3(H + 2 * Hkv, B), dim3(128),
                      0, stream, (const bf16*)qkv, (bf16*)q_out, (bf16*)kc,
                      (bf16*)vc, cosT, sinT, seq_lens, H, Hkv, D, Smax);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_prefill_qkv_prep(const void* qkv, void* q_out, void* k_out,
+                                   void* v_out, const float* cosT,
+                                   const float* sinT, int B, int S, int H,
+                                   int Hkv, int D, int Bc, int Smax, int pos0,
+                                   int table_rows, hipStream_t stream) {
+  // every index the kernel forms is bounded here: no position outside the
+  // tables or the caches reaches it
+  if (B < 1 || S < 1 || H < 1 || Hkv < 1 || D < 8 || D % 8)
+    return hipErrorInvalidValue;
+  if (pos0 < 0 || (long)pos0 + S > table_rows) return hipErrorInvalidValue;
+  const bool cache = Smax > 0;
+  if (Smax < 0 || (cache && ((long)pos0 + S > Smax || Bc < B)))
+    return hipErrorInvalidValue;
+  const long P = (long)(H + 2 * Hkv) * (D / 8);
+  if (P > (1 << 20)) return hipErrorInvalidValue;
+  // tokens per block: the smallest count whose pieces fill whole 256-thread
+  // steps (768 pieces: 1 token, 3 steps; the reranker's 288: 8 tokens, 9
+  // steps), at most 16, doubled up to 4 steps per thread while the grid
+  // still has 1024 blocks
+  int g = PREP_THREADS, r = (int)(P % PREP_THREADS);
+  while (r) { const int x = g % r; g = r; r = x; }
+  int tpb = PREP_THREADS / g;
+  if (tpb > 16) tpb = 16;
+  while (tpb < 16 && tpb * P < 4 * PREP_THREADS &&
+         (long)B * ((S + 2 * tpb - 1) / (2 * tpb)) >= 1024)
+    tpb *= 2;
+  const int nsb = (S + tpb - 1) / tpb;
+  const long blocks = (long)B * nsb;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  if (cache)
+    hipLaunchKernelGGL((prefill_qkv_prep_kernel<true>), dim3((unsigned)blocks),
+                       dim3(PREP_THREADS), 0, stream, (const bf16*)qkv,
+                       (bf16*)q_out, (bf16*)k_out, (bf16*)v_out, cosT, sinT, S,
+                       H, Hkv, D, Smax, pos0, tpb, nsb);
+  else
+    hipLaunchKernelGGL((prefill_qkv_prep_kernel<false>),
+                       dim3((unsigned)blocks), dim3(PREP_THREADS), 0, stream,
+                       (const bf16*)qkv, (bf16*)q_out, (bf16*)k_out,
+                       (bf16*)v_out, cosT, sinT, S, H, Hkv, D, Smax, pos0, tpb,
+                       nsb);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

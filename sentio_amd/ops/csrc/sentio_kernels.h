@@ -17,11 +17,14 @@ hipError_t sentio_rmsnorm_residual(const void* x, const void* res,
                                    const void* w, void* y, void* h, long rows,
                                    int D, float eps, hipStream_t stream);
 // part is fp32 [S, rows, D], slabs summed in increasing s; S sits BEFORE
-// rows and D; writes y and h like sentio_rmsnorm_residual
+// rows and D; writes y and h like sentio_rmsnorm_residual.  Rows of at most
+// 8192 elements keep h in registers between the passes; reread != 0 takes
+// the kernel that loads h back at any row length (tests and probes).
+// Outputs are bit-identical
 hipError_t sentio_rmsnorm_residual_partials(const float* part, const void* res,
                                             const void* w, void* y, void* h,
                                             int S, long rows, int D, float eps,
-                                            hipStream_t stream);
+                                            int reread, hipStream_t stream);
 hipError_t sentio_swiglu(const void* gate, const void* up, void* out, long n,
                          hipStream_t stream);
 // F is the OUTPUT width (half the packed [gate | up] row)
@@ -36,6 +39,17 @@ hipError_t sentio_decode_qkv_prep(const void* qkv, void* q_out, void* kc,
                                   const float* sinT, const int* seq_lens,
                                   int B, int H, int Hkv, int D, int Smax,
                                   hipStream_t stream);
+// qkv is [B, S, (H+2*Hkv)*D]; token (b, s) sits at position pos0 + s.
+// Smax > 0: k_out / v_out are caches [Bc, Hkv, Smax, D], rows pos0 ..
+// pos0+S-1 of batch rows 0 .. B-1 are written; Smax == 0: contiguous
+// [B, S, Hkv, D] outputs (Bc ignored).  hipErrorInvalidValue unless
+// D % 8 == 0, pos0 >= 0, pos0 + S <= table_rows and, with caches,
+// pos0 + S <= Smax and Bc >= B.  Every pointer must be 16-byte aligned
+hipError_t sentio_prefill_qkv_prep(const void* qkv, void* q_out, void* k_out,
+                                   void* v_out, const float* cosT,
+                                   const float* sinT, int B, int S, int H,
+                                   int Hkv, int D, int Bc, int Smax, int pos0,
+                                   int table_rows, hipStream_t stream);
 hipError_t sentio_softmax(const void* x, void* y, long rows, int D,
                           hipStream_t stream);
 hipError_t sentio_mean_pool_l2norm(const void* hidden,

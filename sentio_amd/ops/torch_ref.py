@@ -349,6 +349,38 @@ def decode_qkv_prep(
     return q.view(B, H, D)
 
 
+def prefill_qkv_prep(
+    qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: int,
+    n_heads: int, n_kv_heads: int,
+    k_cache: torch.Tensor | None = None, v_cache: torch.Tensor | None = None,
+):
+    """Reference of ops.prefill_qkv_prep: the split / rope_apply / indexed
+    cache write sequence the fused kernel replaces.  qkv [B, S, (H+2Hkv)*D],
+    token (b, s) at position pos0 + s.  With caches [Bc, Hkv, Smax, D]:
+    writes RoPE(k) and v to rows pos0 .. pos0+S-1 of batch rows < B and
+    returns q [B, S, H, D]; without: returns (q, k, v), k and v
+    [B, S, Hkv, D]."""
+    B, S, W = qkv.shape
+    H, Hkv = n_heads, n_kv_heads
+    D = W // (H + 2 * Hkv)
+    q_end = H * D
+    k_end = q_end + Hkv * D
+    pos = (pos0 + torch.arange(S, device=qkv.device)).unsqueeze(0).expand(B, S)
+    q = qkv[..., :q_end].reshape(B, S, H, D)
+    k = qkv[..., q_end:k_end].reshape(B, S, Hkv, D)
+    v = qkv[..., k_end:].reshape(B, S, Hkv, D)
+    q = rope_apply(q, cos, sin, pos)
+    k = rope_apply(k, cos, sin, pos)
+    if k_cache is None:
+        return q, k, v.contiguous()
+    bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, S)
+    k_cache[bidx.reshape(-1), :, pos.reshape(-1)] = \
+        k.reshape(B * S, Hkv, D).to(k_cache.dtype)
+    v_cache[bidx.reshape(-1), :, pos.reshape(-1)] = \
+        v.reshape(B * S, Hkv, D).to(v_cache.dtype)
+    return q
+
+
 def decode_attention_fused(
     qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor,
