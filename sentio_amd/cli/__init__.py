@@ -132,6 +132,9 @@ def run_all(
                                        help="Service-wide sampling top-k"),
     seed: int = typer.Option(None, "--seed", min=0,
                              help="Pin every request's sampling seed"),
+    regex: str = typer.Option(None, "--regex",
+                              help="Constrain every answer that brings no "
+                                   "response_format to this regex"),
 ):
     """Start the full stack: API server (the built-in /ui page is the UI —
     reference `sentio run all` spawned API + Streamlit + Qdrant docker;
@@ -142,6 +145,14 @@ def run_all(
     from sentio_amd.serving.app import create_app
 
     apply_sampling_defaults(settings, top_p, sampling_top_k, seed)
+    if regex:
+        from sentio_amd.serving.handlers import compile_response_format
+
+        try:
+            compile_response_format({"type": "regex", "pattern": regex})
+        except ValueError as exc:
+            raise typer.BadParameter(str(exc), param_hint="--regex")
+        settings.gen_regex = regex
 
     resolved_port = port or settings.api_port
     typer.echo(f"serving API + UI on http://{host or settings.api_host}:"

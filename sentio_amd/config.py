@@ -107,6 +107,8 @@ class Settings:
     dynamic_batching: bool = True           # batch concurrent /chat generations
     continuous_batching: bool = True        # requests join decode mid-flight
     slot_sampling: bool = False             # top-k/top-p requests join the slot loop
+    verifier_constrained: bool = False      # verifier decodes under VERDICT_GRAMMAR
+    gen_regex: str = ""                     # service-wide default response_format regex
     batch_wait_ms: float = 8.0
     device: str = "auto"                    # auto | cuda | cpu
 
@@ -160,6 +162,8 @@ class Settings:
         "dynamic_batching": "DYNAMIC_BATCHING",
         "continuous_batching": "CONTINUOUS_BATCHING",
         "slot_sampling": "SLOT_SAMPLING",
+        "verifier_constrained": "VERIFIER_CONSTRAINED",
+        "gen_regex": "GEN_REGEX",
         "batch_wait_ms": "BATCH_WAIT_MS",
         "device": "SENTIO_DEVICE",
         "enable_metrics": "ENABLE_METRICS",

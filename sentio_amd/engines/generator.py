@@ -12,7 +12,7 @@ Temperature-per-mode mirrors reference generator.py:262-267
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Iterator
+from typing import Any, Callable, Iterator
 
 import torch
 
@@ -35,6 +35,8 @@ class SamplingParams:
     top_k: int = 0
     top_p: float = 1.0
     seed: int | None = None
+    # a Grammar or a GrammarHandle of the engine: constrained decoding
+    grammar: Any = None
 
     @property
     def filtered(self) -> bool:
@@ -42,6 +44,19 @@ class SamplingParams:
         (ops.sample_filtered) instead of the default sampling path."""
         return (int(self.top_k or 0) > 0 or float(self.top_p) < 1.0
                 or self.seed is not None)
+
+
+@dataclass(frozen=True, eq=False)
+class GrammarHandle:
+    """A grammar registered with an engine: where its states sit in the
+    engine-wide table.  `min_tokens` = dist[start], the smallest token
+    budget a request with this grammar can have."""
+
+    index: int
+    start: int          # global start state
+    n_states: int       # with DONE
+    min_tokens: int
+    grammar: Any
 
 
 class SlotSampler:
@@ -62,11 +77,20 @@ class SlotSampler:
         self.seed = torch.zeros(S, dtype=torch.int64, device=dev)
         self.step = torch.zeros(S, dtype=torch.int32, device=dev)
         self.active = torch.zeros(S, dtype=torch.uint8, device=dev)
+        # automaton state and remaining budget of constrained slots;
+        # state = -1: the slot samples unconstrained
+        self.state = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.left = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._constrained: set[int] = set()
 
     @torch.inference_mode()
-    def admit(self, rows: list[int], params: list[SamplingParams]) -> None:
+    def admit(self, rows: list[int], params: list[SamplingParams],
+              max_new: list[int] | None = None) -> None:
         """Write each request's parameters into its slot: step = 0,
-        active = 1.  A request without a seed gets engine.derive_seed()."""
+        active = 1.  A request without a seed gets engine.derive_seed().
+        A request with a grammar starts at the grammar's start state with
+        left = its max_new entry (ValueError when that is below the
+        grammar's shortest completion); the others get state = -1."""
         rows = [int(r) for r in rows]
         if any(r < 0 or r >= self.slots for r in rows) \
                 or len(set(rows)) != len(rows):
@@ -76,6 +100,15 @@ class SlotSampler:
                              f"{len(rows)} rows")
         if not rows:
             return
+        handles = [self.engine.resolve_grammar(p.grammar) for p in params]
+        budgets = [0] * len(rows)
+        if any(h is not None for h in handles):
+            if max_new is None or len(max_new) != len(rows):
+                raise ValueError("constrained slots need max_new per row")
+            for i, h in enumerate(handles):
+                if h is not None:
+                    budgets[i] = int(max_new[i])
+                    self.engine.check_grammar_budget(h, budgets[i])
         dev = self.engine.device
         seeds = [int(p.seed) if p.seed is not None
                  else self.engine.derive_seed() for p in params]
@@ -92,11 +125,21 @@ class SlotSampler:
         self.seed[idx] = torch.tensor(seeds, dtype=torch.int64, device=dev)
         self.step[idx] = 0
         self.active[idx] = 1
+        self.state[idx] = torch.tensor(
+            [h.start if h is not None else -1 for h in handles],
+            dtype=torch.int32, device=dev)
+        self.left[idx] = torch.tensor(budgets, dtype=torch.int32, device=dev)
+        for r, h in zip(rows, handles):
+            if h is not None:
+                self._constrained.add(r)
+            else:
+                self._constrained.discard(r)
 
     @torch.inference_mode()
     def release(self, row: int) -> None:
         """The slot is free: later sample() calls skip it."""
         self.active[int(row)] = 0
+        self._constrained.discard(int(row))
 
     @torch.inference_mode()
     def sample(self, logits: torch.Tensor, cur: torch.Tensor,
@@ -106,8 +149,15 @@ class SlotSampler:
         the admission call, logits [len(rows), V] scattered to those slots
         (their step-0 draw; ops.sample_slots checks the list for range and
         duplicates).  Without: the per-step call, logits [S, V]."""
-        ops.sample_slots(logits, rows, self.temperature, self.top_k,
-                         self.top_p, self.seed, self.step, self.active, cur)
+        if not self._constrained:
+            ops.sample_slots(logits, rows, self.temperature, self.top_k,
+                             self.top_p, self.seed, self.step, self.active,
+                             cur)
+            return
+        ops.sample_slots_constrained(
+            logits, rows, self.temperature, self.top_k, self.top_p, self.seed,
+            self.step, self.active, cur, self.state, self.left,
+            self.engine.grammar_tables())
 
 
 class _DecodeSession:
@@ -234,6 +284,11 @@ class GeneratorEngine:
         import threading
 
         self._gen_lock = threading.Lock()   # decode sessions hold static state
+        # registered grammars: one append-only table, global state numbers
+        self._grammar_handles: dict = {}
+        self._grammar_host: list = []       # per grammar (next, mask, dist)
+        self._grammar_states = 0
+        self._grammar_tables = None         # ops.GrammarTables on the device
 
     def _new_cache(self, batch: int, max_seq: int) -> KVCache:
         """A session cache, in the engine's KV dtype."""
@@ -313,6 +368,68 @@ class GeneratorEngine:
                            .clamp_min(2.0 ** -20).cpu())
         self.set_kv_scales(ks, vs)
         return ks, vs
+
+    # ----- grammar-constrained decoding -----
+    def register_grammar(self, grammar) -> GrammarHandle:
+        """Build the grammar's token tables (once per distinct grammar) and
+        append them to the engine-wide device table.  States are numbered
+        globally and the table only grows, so states held by running
+        requests stay valid.  At most 32766 states in all."""
+        import numpy as np
+
+        from sentio_amd.engines.grammar import MAX_STATES, Grammar
+
+        if not isinstance(grammar, Grammar):
+            raise ValueError("register_grammar takes a Grammar")
+        key = grammar.pattern or id(grammar)
+        with self._gen_lock:
+            hit = self._grammar_handles.get(key)
+            if hit is not None:
+                return hit
+            tb = grammar.token_tables(self.tokenizer)
+            base, n = self._grammar_states, tb.n_states
+            if base + n > MAX_STATES + 1:
+                raise ValueError(
+                    f"grammar table full: {base} states registered, this "
+                    f"grammar needs {n}, the limit is {MAX_STATES + 1}")
+            nxt = np.where(tb.next >= 0, tb.next.astype(np.int32) + base,
+                           -1).astype(np.int16)
+            self._grammar_host.append((nxt, tb.mask, tb.dist))
+            self._grammar_states = base + n
+            self._grammar_tables = ops.GrammarTables.from_numpy(
+                np.concatenate([h[0] for h in self._grammar_host]),
+                np.concatenate([h[1] for h in self._grammar_host]),
+                np.concatenate([h[2] for h in self._grammar_host]),
+                device=self.device)
+            handle = GrammarHandle(len(self._grammar_host) - 1,
+                                   base + tb.start, n, int(tb.dist[tb.start]),
+                                   grammar)
+            self._grammar_handles[key] = handle
+            return handle
+
+    def resolve_grammar(self, grammar) -> GrammarHandle | None:
+        """None, a handle of this engine or a Grammar (registered on first
+        use) -> handle."""
+        if grammar is None:
+            return None
+        if isinstance(grammar, GrammarHandle):
+            g = grammar.grammar
+            if self._grammar_handles.get(g.pattern or id(g)) is not grammar:
+                raise ValueError("grammar handle of another engine")
+            return grammar
+        return self.register_grammar(grammar)
+
+    @staticmethod
+    def check_grammar_budget(handle: GrammarHandle, max_new_tokens: int):
+        if handle.min_tokens > int(max_new_tokens):
+            raise ValueError(
+                f"max_new_tokens={int(max_new_tokens)} is below the "
+                f"grammar's shortest completion ({handle.min_tokens} tokens)")
+
+    def grammar_tables(self):
+        """The current engine-wide ops.GrammarTables (None before the first
+        registration)."""
+        return self._grammar_tables
 
     # ----- prefix-KV cache (shared prompt prefixes prefilled once) -----
     _PREFIX_MIN_TOKENS = 64
@@ -503,6 +620,7 @@ class GeneratorEngine:
         top_k: int = 0,
         top_p: float = 1.0,
         seed: int | None = None,
+        grammar=None,
     ) -> list[str]:
         """Batched generation.  Returns decoded completions (prompt excluded).
 
@@ -513,12 +631,22 @@ class GeneratorEngine:
         path (ops.sample_token).  Otherwise every step samples through
         ops.sample_filtered; prompt i draws with seed + i, so a seeded
         request reproduces its text whatever else shares the engine.
+
+        grammar (a Grammar or a handle from register_grammar): every row
+        decodes under the grammar through ops.sample_constrained at any
+        temperature, with left = max_new_tokens, so each completion matches
+        the grammar even when the budget runs out.  ValueError, before any
+        forward, when max_new_tokens is below the grammar's shortest
+        completion.
         """
         if not prompts:
             return []
         # a request cannot generate past the cache: clamp so the prompt
         # budget stays positive and decode never writes beyond max_seq
         max_new_tokens = max(1, min(max_new_tokens, self.max_seq - 9))
+        handle = self.resolve_grammar(grammar)
+        if handle is not None:
+            self.check_grammar_budget(handle, max_new_tokens)
         import time as _time
 
         from sentio_amd.observability.kernel_timer import get_timer
@@ -529,7 +657,7 @@ class GeneratorEngine:
                 return self._generate_locked(
                     prompts, max_new_tokens, temperature, stop_on_eos,
                     on_token, _time,
-                    SamplingParams(temperature, top_k, top_p, seed))
+                    SamplingParams(temperature, top_k, top_p, seed, handle))
         finally:
             self._gen_lock.release()
 
@@ -595,7 +723,8 @@ class GeneratorEngine:
         # (every 16 steps) or the streaming callback — not per token.
         toks_buf = torch.zeros(B, max_new_tokens, dtype=torch.int64,
                                device=self.device)
-        sampler = self._make_sampler(sampling, temperature, B)
+        sampler = self._make_sampler(sampling, temperature, B,
+                                     max_new_tokens)
         cur = sampler(logits, 0)
         n_steps = max_new_tokens
         for step in range(max_new_tokens):
@@ -647,12 +776,17 @@ class GeneratorEngine:
         return (n * 0x9E3779B1 + 909) & 0x7FFFFFFF
 
     def _make_sampler(self, sampling: SamplingParams | None,
-                      temperature: float, batch: int):
+                      temperature: float, batch: int,
+                      max_new_tokens: int = 0):
         """sampler(logits, step) for one generate/stream call.  Default
         parameters: the present path (_sample -> ops.sample_token, same
         seeds, same tokens).  Otherwise ops.sample_filtered with per-row
-        arrays built once; only the step counter changes per token."""
-        if sampling is None or not sampling.filtered:
+        arrays built once; only the step counter changes per token.  With a
+        grammar: ops.sample_constrained for any parameters, every row (the
+        padding rows of a bucketed batch too) from the grammar's start
+        state with left = max_new_tokens."""
+        handle = sampling.grammar if sampling is not None else None
+        if handle is None and (sampling is None or not sampling.filtered):
             return lambda logits, _step: self._sample(logits, temperature)
         dev = self.device
         base = sampling.seed if sampling.seed is not None \
@@ -662,6 +796,21 @@ class GeneratorEngine:
                         device=dev)
         ps = torch.full((batch,), float(sampling.top_p), device=dev)
         seeds = int(base) + torch.arange(batch, dtype=torch.int64, device=dev)
+
+        if handle is not None:
+            tables = self._grammar_tables
+            state = torch.full((batch,), int(handle.start), dtype=torch.int32,
+                               device=dev)
+            left = torch.full((batch,), int(max_new_tokens),
+                              dtype=torch.int32, device=dev)
+
+            def constrained(logits, step):
+                steps = torch.full((batch,), int(step), dtype=torch.int32,
+                                   device=dev)
+                return ops.sample_constrained(logits, temps, ks, ps, seeds,
+                                              steps, state, left, tables)
+
+            return constrained
 
         def sampler(logits, step):
             steps = torch.full((batch,), int(step), dtype=torch.int32,
@@ -673,26 +822,31 @@ class GeneratorEngine:
     @torch.inference_mode()
     def stream(self, prompt: str, max_new_tokens: int = 128,
                temperature: float = 0.3, top_k: int = 0, top_p: float = 1.0,
-               seed: int | None = None) -> Iterator[str]:
+               seed: int | None = None, grammar=None) -> Iterator[str]:
         """Yield text deltas token-by-token (single prompt) — the on-device
         equivalent of the reference's SSE streaming (openai.py:149-157).
         Holds the generation lock for the stream's duration (the pooled
         decode sessions are engine-level state)."""
+        handle = self.resolve_grammar(grammar)
+        if handle is not None:
+            self.check_grammar_budget(handle, max_new_tokens)
         with self._gen_lock:
             yield from self._stream_locked(prompt, max_new_tokens, temperature,
-                                           top_k, top_p, seed)
+                                           top_k, top_p, seed, handle)
 
     def _stream_locked(self, prompt: str, max_new_tokens: int,
                        temperature: float, top_k: int = 0,
                        top_p: float = 1.0,
-                       seed: int | None = None) -> Iterator[str]:
+                       seed: int | None = None,
+                       grammar=None) -> Iterator[str]:
         prompt_budget = self.max_seq - max_new_tokens - 1
         ids = self.tokenizer.encode(prompt[-4 * prompt_budget:], prompt_budget)
         tokens = torch.tensor([ids], dtype=torch.int64, device=self.device)
         sess = self._decode_session(1, self.max_seq)
         logits = sess.prefill(tokens)
         sampler = self._make_sampler(
-            SamplingParams(temperature, top_k, top_p, seed), temperature, 1)
+            SamplingParams(temperature, top_k, top_p, seed, grammar),
+            temperature, 1, max_new_tokens)
         cur = sampler(logits, 0)
         generated: list[int] = []
         emitted = ""

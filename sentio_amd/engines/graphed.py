@@ -32,6 +32,38 @@ def graphs_enabled(device: str) -> bool:
 _gc_lock = threading.Lock()
 _gc_depth = 0
 _gc_was_enabled = False
+_prime_lock = threading.Lock()
+_primed = False
+_prime_keep = None      # the priming graph and its buffer, kept for good
+
+
+def prime_capture_state() -> None:
+    """Make the process's FIRST graph capture outside inference mode.
+
+    The default CUDA generator creates its capture-time seed / offset
+    tensors when the first graph registers with it, drops them when the
+    last registered graph dies, and every capture updates them in place.
+    The engines capture under torch.inference_mode(): if theirs is the
+    first live graph those tensors are inference tensors, and any capture
+    made OUTSIDE inference mode while an engine graph lives (user code, a
+    test) fails with "Inplace update to inference tensor outside
+    InferenceMode" and leaves the generator stuck in capture mode.  One
+    trivial graph captured with inference mode switched off, and never
+    freed, creates them as ordinary tensors and keeps them: both kinds of
+    capture can update those."""
+    global _primed, _prime_keep
+    if _primed or not torch.cuda.is_available():
+        return
+    with _prime_lock:
+        if _primed:
+            return
+        with torch.inference_mode(False):
+            buf = torch.zeros(1, device="cuda")
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="relaxed"):
+                buf.add_(1)
+            _prime_keep = (graph, buf)
+        _primed = True
 
 
 @contextlib.contextmanager
@@ -48,6 +80,7 @@ def capture_gc_guard():
     then hold automatic collection off until the capture has ended.
     Re-entrant across threads (captures on two threads may overlap)."""
     global _gc_depth, _gc_was_enabled
+    prime_capture_state()
     with _gc_lock:
         if _gc_depth == 0:
             _gc_was_enabled = gc.isenabled()

@@ -81,8 +81,9 @@ class MockGeneratorEngine:
     def generate(self, prompts: list[str], max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
                  on_token=None, top_k: int = 0, top_p: float = 1.0,
-                 seed: int | None = None) -> list[str]:
-        # top_k / top_p / seed: accepted for signature parity, ignored
+                 seed: int | None = None, grammar=None) -> list[str]:
+        # top_k / top_p / seed / grammar: accepted for signature parity,
+        # ignored
         outs = []
         for p in prompts:
             h = hashlib.sha256(p.encode()).hexdigest()[:8]
@@ -94,7 +95,7 @@ class MockGeneratorEngine:
 
     def stream(self, prompt: str, max_new_tokens: int = 128,
                temperature: float = 0.3, top_k: int = 0, top_p: float = 1.0,
-               seed: int | None = None):
+               seed: int | None = None, grammar=None):
         text = self.generate([prompt])[0]
         for i in range(0, len(text), 24):
             yield text[i : i + 24]

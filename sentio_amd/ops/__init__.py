@@ -546,6 +546,46 @@ def _check_slot_array(t, name: str, n: int, dtype, device) -> None:
                          f"on {device}")
 
 
+def _check_slot_call(logits, slot, temperature, top_k, top_p, seed, step,
+                     active, tok, int32_extra=()):
+    """The argument checks both slot-table samplers share; `int32_extra`:
+    further (tensor, name) int32 [S] arrays.  Returns the slot list as an
+    int32 tensor (or None / the tensor given)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 \
+            or logits.dtype != torch.float32 or logits.numel() == 0:
+        raise ValueError("logits must be a non-empty float32 [R, V] tensor")
+    if not isinstance(tok, torch.Tensor) or tok.dim() != 1 \
+            or tok.numel() == 0:
+        raise ValueError("tok must be a non-empty int64 [S] tensor")
+    R, S, dev = logits.shape[0], tok.shape[0], logits.device
+    _check_slot_array(tok, "tok", S, torch.int64, dev)
+    _check_slot_array(temperature, "temperature", S, torch.float32, dev)
+    _check_slot_array(top_k, "top_k", S, torch.int32, dev)
+    _check_slot_array(top_p, "top_p", S, torch.float32, dev)
+    _check_slot_array(seed, "seed", S, torch.int64, dev)
+    _check_slot_array(step, "step", S, torch.int32, dev)
+    for t, name in int32_extra:
+        _check_slot_array(t, name, S, torch.int32, dev)
+    if active is not None:
+        _check_slot_array(active, "active", S, torch.uint8, dev)
+    if slot is None:
+        if R != S:
+            raise ValueError(f"without a slot table logits must have one row "
+                             f"per slot: {R} rows for {S} slots")
+    elif isinstance(slot, torch.Tensor):
+        _check_slot_array(slot, "slot", R, torch.int32, dev)
+    else:
+        slot = [int(s) for s in slot]
+        if len(slot) != R:
+            raise ValueError(f"{len(slot)} slots for {R} logits rows")
+        if any(s < 0 or s >= S for s in slot):
+            raise ValueError(f"slots {slot} outside [0, {S})")
+        if len(set(slot)) != len(slot):
+            raise ValueError(f"duplicate slots in {slot}")
+        slot = torch.tensor(slot, dtype=torch.int32, device=dev)
+    return slot
+
+
 def sample_slots(logits, slot, temperature, top_k, top_p, seed, step, active,
                  tok) -> None:
     """ops.sample_filtered over a table of S persistent slots, IN PLACE on
@@ -564,42 +604,143 @@ def sample_slots(logits, slot, temperature, top_k, top_p, seed, step, active,
     logits[r] with slot s's parameters at step[s], then step[s] += 1.
     Skipped slots keep tok[s] and step[s].  CPU and GPU agree on the support
     and on greedy rows, not on the stochastic pick."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 \
-            or logits.dtype != torch.float32 or logits.numel() == 0:
-        raise ValueError("logits must be a non-empty float32 [R, V] tensor")
-    if not isinstance(tok, torch.Tensor) or tok.dim() != 1 \
-            or tok.numel() == 0:
-        raise ValueError("tok must be a non-empty int64 [S] tensor")
-    R, S, dev = logits.shape[0], tok.shape[0], logits.device
-    _check_slot_array(tok, "tok", S, torch.int64, dev)
-    _check_slot_array(temperature, "temperature", S, torch.float32, dev)
-    _check_slot_array(top_k, "top_k", S, torch.int32, dev)
-    _check_slot_array(top_p, "top_p", S, torch.float32, dev)
-    _check_slot_array(seed, "seed", S, torch.int64, dev)
-    _check_slot_array(step, "step", S, torch.int32, dev)
-    if active is not None:
-        _check_slot_array(active, "active", S, torch.uint8, dev)
-    if slot is None:
-        if R != S:
-            raise ValueError(f"without a slot table logits must have one row "
-                             f"per slot: {R} rows for {S} slots")
-    elif isinstance(slot, torch.Tensor):
-        _check_slot_array(slot, "slot", R, torch.int32, dev)
-    else:
-        slot = [int(s) for s in slot]
-        if len(slot) != R:
-            raise ValueError(f"{len(slot)} slots for {R} logits rows")
-        if any(s < 0 or s >= S for s in slot):
-            raise ValueError(f"slots {slot} outside [0, {S})")
-        if len(set(slot)) != len(slot):
-            raise ValueError(f"duplicate slots in {slot}")
-        slot = torch.tensor(slot, dtype=torch.int32, device=dev)
+    slot = _check_slot_call(logits, slot, temperature, top_k, top_p, seed,
+                            step, active, tok)
     if _on_gpu(logits):
         _require_hip().sample_slots(logits.contiguous(), slot, temperature,
                                     top_k, top_p, seed, step, active, tok)
         return
     torch_ref.sample_slots(logits, slot, temperature, top_k, top_p, seed,
                            step, active, tok)
+
+
+class GrammarTables:
+    """The device tables of constrained sampling (see engines/grammar.py):
+    next int16 [N, Vt], mask int32 [N, ceil(Vt/32)], dist int16 [N], plus
+    max_dist, the largest dist entry (a host int: the kernel skips the dist
+    lookup for rows whose budget cannot bind)."""
+
+    def __init__(self, next, mask, dist, max_dist: int | None = None):
+        for t, name, dt, nd in ((next, "next", torch.int16, 2),
+                                (mask, "mask", torch.int32, 2),
+                                (dist, "dist", torch.int16, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt \
+                    or t.dim() != nd or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} "
+                                 f"{nd}-d tensor")
+        N, Vt = next.shape
+        if not (1 <= N <= 32767) or Vt < 1:
+            raise ValueError(f"next must be [N <= 32767, Vt], got "
+                             f"{tuple(next.shape)}")
+        if tuple(mask.shape) != (N, (Vt + 31) // 32):
+            raise ValueError(f"mask must be [{N}, {(Vt + 31) // 32}], got "
+                             f"{tuple(mask.shape)}")
+        if mask.shape[1] > 2048:
+            raise ValueError("at most 65536 tokenizer entries")
+        if tuple(dist.shape) != (N,):
+            raise ValueError(f"dist must be [{N}], got {tuple(dist.shape)}")
+        if next.device != mask.device or next.device != dist.device:
+            raise ValueError("next, mask and dist must share a device")
+        self.next, self.mask, self.dist = next, mask, dist
+        self.max_dist = int(dist.max()) if max_dist is None else int(max_dist)
+
+    @classmethod
+    def from_numpy(cls, next, mask, dist, device="cpu") -> "GrammarTables":
+        import numpy as np
+
+        return cls(
+            torch.from_numpy(np.ascontiguousarray(next)).to(device),
+            torch.from_numpy(np.ascontiguousarray(mask)).to(device),
+            torch.from_numpy(np.ascontiguousarray(dist)).to(device),
+            int(np.max(dist)))
+
+    @property
+    def n_states(self) -> int:
+        return int(self.next.shape[0])
+
+    @property
+    def vocab(self) -> int:
+        return int(self.next.shape[1])
+
+    @property
+    def device(self):
+        return self.next.device
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size()
+                   for t in (self.next, self.mask, self.dist))
+
+
+def _check_tables(tables, device) -> None:
+    if not isinstance(tables, GrammarTables):
+        raise ValueError("tables must be an ops.GrammarTables")
+    if tables.device != device:
+        raise ValueError(f"grammar tables are on {tables.device}, logits on "
+                         f"{device}")
+
+
+def sample_constrained(logits, temperature, top_k, top_p, seed, step, state,
+                       left, tables):
+    """Grammar-constrained ops.sample_filtered, IN PLACE on `state` and
+    `left` (contiguous int32 [B] on the logits' device).
+
+    A row in state s (0 <= s < N) with `left` tokens remaining, this one
+    included, may pick v iff v < min(V, Vt), bit v of mask[s] is set and
+    dist[next[s, v]] <= left - 1.  Every other logit counts as -inf; the
+    rest is sample_filtered's arithmetic (same noise for the same (seed,
+    step, v)).  Then state = next[s, tok] and left -= 1.  If every allowed
+    logit is -inf or NaN the row takes the lowest allowed index.  Callers
+    establish dist[state] <= left; the rule keeps it, so a row always ends
+    in an accepting state.  A row with state < 0 is unconstrained: exactly
+    sample_filtered over all V logits, state and left untouched (the GPU
+    treats state >= N the same way; on the CPU, where the host owns the
+    array, that is a ValueError).  Returns tok [B] int64."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 \
+            or logits.numel() == 0:
+        raise ValueError("logits must be a non-empty [B, V] tensor")
+    B, dev = logits.shape[0], logits.device
+    _check_tables(tables, dev)
+    _check_slot_array(state, "state", B, torch.int32, dev)
+    _check_slot_array(left, "left", B, torch.int32, dev)
+    t = _row_tensor(temperature, B, torch.float32, dev)
+    k = _row_tensor(top_k, B, torch.int32, dev)
+    p = _row_tensor(top_p, B, torch.float32, dev)
+    sd = _row_tensor(seed, B, torch.int64, dev)
+    st = _row_tensor(step, B, torch.int32, dev)
+    if _on_gpu(logits):
+        return _require_hip().sample_constrained(
+            logits.contiguous(), t, k, p, sd, st, state, left, tables.next,
+            tables.mask, tables.dist, tables.max_dist)
+    if bool((state >= tables.n_states).any()):
+        raise ValueError(f"state outside the table's {tables.n_states} states")
+    return torch_ref.sample_constrained(logits, t, k, p, sd, st, state, left,
+                                        tables.next, tables.mask, tables.dist)
+
+
+def sample_slots_constrained(logits, slot, temperature, top_k, top_p, seed,
+                             step, active, tok, state, left, tables) -> None:
+    """ops.sample_slots with a per-slot automaton: `state` and `left` are
+    contiguous int32 [S] tensors on the logits' device, updated in place
+    like `step` and `tok`.  Slot s samples as ops.sample_constrained does
+    with (state[s], left[s]) at step[s]; state[s] < 0 is an unconstrained
+    slot, sampled exactly as ops.sample_slots samples it.  Skipped slots
+    keep tok, step, state and left."""
+    slot = _check_slot_call(logits, slot, temperature, top_k, top_p, seed,
+                            step, active, tok,
+                            ((state, "state"), (left, "left")))
+    _check_tables(tables, logits.device)
+    if _on_gpu(logits):
+        _require_hip().sample_slots_constrained(
+            logits.contiguous(), slot, temperature, top_k, top_p, seed, step,
+            active, tok, state, left, tables.next, tables.mask, tables.dist,
+            tables.max_dist)
+        return
+    if bool((state >= tables.n_states).any()):
+        raise ValueError(f"state outside the table's {tables.n_states} states")
+    torch_ref.sample_slots_constrained(
+        logits, slot, temperature, top_k, top_p, seed, step, active, tok,
+        state, left, tables.next, tables.mask, tables.dist)
 
 
 def skinny_gemm(x, w):
@@ -670,5 +811,5 @@ def gemm_bf16(a, b):
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
-    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
+    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

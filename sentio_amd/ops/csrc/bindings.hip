@@ -312,6 +312,120 @@ void sample_slots(torch::Tensor logits, c10::optional<torch::Tensor> slot,
       stream()), "sample_slots");
 }
 
+// The grammar tables of constrained sampling: next int16 [N, Vt], mask int32
+// [N, ceil(Vt/32)], dist int16 [N], contiguous on the logits' device.
+struct GrammarTables {
+  int N, Vt, W;
+};
+GrammarTables check_tables(const torch::Tensor& next, const torch::Tensor& mask,
+                           const torch::Tensor& dist, const torch::Tensor& like,
+                           int64_t max_dist) {
+  auto on = [&](const torch::Tensor& t, torch::ScalarType dt, int64_t dim,
+                const char* name) {
+    TORCH_CHECK(t.dim() == dim && t.scalar_type() == dt && t.is_contiguous() &&
+                t.device() == like.device(), name, " must be a contiguous ",
+                dim, "-d tensor of its kernel dtype on the logits' device");
+  };
+  on(next, torch::kShort, 2, "next");
+  on(mask, torch::kInt, 2, "mask");
+  on(dist, torch::kShort, 1, "dist");
+  const int64_t N = next.size(0), Vt = next.size(1);
+  TORCH_CHECK(N >= 1 && N <= 32767 && Vt >= 1, "next must be [N <= 32767, Vt]");
+  TORCH_CHECK(mask.size(0) == N && mask.size(1) == (Vt + 31) / 32,
+              "mask must be [N, ceil(Vt/32)]");
+  TORCH_CHECK(mask.size(1) <= 2048, "at most 65536 tokenizer entries");
+  TORCH_CHECK(dist.size(0) == N, "dist must be [N]");
+  TORCH_CHECK(max_dist >= 0 && max_dist <= 32767, "bad max_dist");
+  return {(int)N, (int)Vt, (int)mask.size(1)};
+}
+
+// In place on state and left (int32 [B]); returns tok [B] int64.
+torch::Tensor sample_constrained(torch::Tensor logits,
+                                 torch::Tensor temperature, torch::Tensor top_k,
+                                 torch::Tensor top_p, torch::Tensor seed,
+                                 torch::Tensor step, torch::Tensor state,
+                                 torch::Tensor left, torch::Tensor next,
+                                 torch::Tensor mask, torch::Tensor dist,
+                                 int64_t max_dist) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "logits must be [B,V] GPU");
+  auto l = logits.to(torch::kFloat).contiguous();
+  const long B = l.size(0);
+  TORCH_CHECK(B > 0 && l.size(1) > 0, "logits must be non-empty");
+  auto t = row_param(temperature, l, torch::kFloat, "temperature");
+  auto k = row_param(top_k, l, torch::kInt, "top_k");
+  auto p = row_param(top_p, l, torch::kFloat, "top_p");
+  auto sd = row_param(seed, l, torch::kLong, "seed");
+  auto st = row_param(step, l, torch::kInt, "step");
+  auto inplace = [&](const torch::Tensor& x, const char* name) {
+    TORCH_CHECK(x.dim() == 1 && x.size(0) == B &&
+                x.scalar_type() == torch::kInt && x.is_contiguous() &&
+                x.device() == l.device(), name,
+                " must be a contiguous int32 [B] tensor on the logits' device");
+  };
+  inplace(state, "state");
+  inplace(left, "left");
+  const GrammarTables g = check_tables(next, mask, dist, l, max_dist);
+  auto out = torch::empty({B}, l.options().dtype(torch::kLong));
+  check_hip(sentio_sample_constrained(
+      l.data_ptr<float>(), t.data_ptr<float>(), k.data_ptr<int>(),
+      p.data_ptr<float>(), (const long*)sd.data_ptr<int64_t>(),
+      st.data_ptr<int>(), state.data_ptr<int>(), left.data_ptr<int>(),
+      (const short*)next.data_ptr<int16_t>(), mask.data_ptr<int>(),
+      (const short*)dist.data_ptr<int16_t>(), (long*)out.data_ptr<int64_t>(),
+      B, (int)l.size(1), g.Vt, g.N, g.W, (int)max_dist, stream()),
+      "sample_constrained");
+  return out;
+}
+
+// sample_slots with per-slot automaton state: in place on step, tok, state
+// and left, so nothing is converted or copied.
+void sample_slots_constrained(
+    torch::Tensor logits, c10::optional<torch::Tensor> slot,
+    torch::Tensor temperature, torch::Tensor top_k, torch::Tensor top_p,
+    torch::Tensor seed, torch::Tensor step,
+    c10::optional<torch::Tensor> active, torch::Tensor tok,
+    torch::Tensor state, torch::Tensor left, torch::Tensor next,
+    torch::Tensor mask, torch::Tensor dist, int64_t max_dist) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+              logits.scalar_type() == torch::kFloat && logits.is_contiguous(),
+              "logits must be a contiguous f32 [R,V] GPU tensor");
+  const long R = logits.size(0);
+  const long S = tok.numel();
+  TORCH_CHECK(R > 0 && S > 0 && logits.size(1) > 0,
+              "logits and slots must be non-empty");
+  auto slot_arr = [&](const torch::Tensor& t, torch::ScalarType dt, long n,
+                      const char* name) {
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.scalar_type() == dt &&
+                t.is_contiguous() && t.device() == logits.device(), name,
+                " must be a contiguous [", n, "] tensor of its kernel dtype "
+                "on the logits' device");
+  };
+  slot_arr(tok, torch::kLong, S, "tok");
+  slot_arr(temperature, torch::kFloat, S, "temperature");
+  slot_arr(top_k, torch::kInt, S, "top_k");
+  slot_arr(top_p, torch::kFloat, S, "top_p");
+  slot_arr(seed, torch::kLong, S, "seed");
+  slot_arr(step, torch::kInt, S, "step");
+  slot_arr(state, torch::kInt, S, "state");
+  slot_arr(left, torch::kInt, S, "left");
+  if (slot.has_value()) slot_arr(*slot, torch::kInt, R, "slot");
+  else TORCH_CHECK(R == S, "without a slot table logits must be [S,V]");
+  if (active.has_value()) slot_arr(*active, torch::kByte, S, "active");
+  const GrammarTables g = check_tables(next, mask, dist, logits, max_dist);
+  check_hip(sentio_sample_slots_constrained(
+      logits.data_ptr<float>(),
+      slot.has_value() ? slot->data_ptr<int>() : nullptr,
+      temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p.data_ptr<float>(), (const long*)seed.data_ptr<int64_t>(),
+      step.data_ptr<int>(),
+      active.has_value() ? active->data_ptr<uint8_t>() : nullptr,
+      (long*)tok.data_ptr<int64_t>(), state.data_ptr<int>(),
+      left.data_ptr<int>(), (const short*)next.data_ptr<int16_t>(),
+      mask.data_ptr<int>(), (const short*)dist.data_ptr<int16_t>(), R, (int)S,
+      (int)logits.size(1), g.Vt, g.N, g.W, (int)max_dist, stream()),
+      "sample_slots_constrained");
+}
+
 torch::Tensor cosine_scores(torch::Tensor q, torch::Tensor mat) {
   TORCH_CHECK(q.is_cuda() && mat.is_cuda(), "must be on GPU");
   TORCH_CHECK(q.scalar_type() == mat.scalar_type(), "q/mat dtype mismatch");
@@ -764,6 +878,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_support", &sample_support);
   m.def("sample_filtered", &sample_filtered);
   m.def("sample_slots", &sample_slots);
+  m.def("sample_constrained", &sample_constrained);
+  m.def("sample_slots_constrained", &sample_slots_constrained);
   m.def("cosine_scores", &cosine_scores);
   m.def("bm25_score", &bm25_score);
   m.def("flash_attn", &flash_attn);

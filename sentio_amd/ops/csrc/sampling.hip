@@ -117,6 +117,19 @@ __device__ __forceinline__ void sf_foreach(const float* __restrict__ lb, int V,
   }
 }
 
+// The same visit through a filter: `allow(x, v)` passes x on or returns
+// -inf.  SfAll keeps every token, ScAllowed (constrained decoding) the
+// tokens of the row's allowed bitset.
+struct SfAll {
+  __device__ __forceinline__ float operator()(float x, int) const { return x; }
+};
+
+template <class A, class F>
+__device__ __forceinline__ void sf_foreach(const float* __restrict__ lb, int V,
+                                           const A& allow, F&& g) {
+  sf_foreach(lb, V, [&](float x, int v) { g(allow(x, v), v); });
+}
+
 __device__ __forceinline__ u64 sf_block_sum64(u64 v, SfShared& sh) {
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
 #pragma unroll
@@ -140,10 +153,11 @@ __device__ __forceinline__ u64 sf_block_sum64(u64 v, SfShared& sh) {
 // reaches the target.  pfrac >= 0 (mass mode, no top-k) sets the target to
 // pfrac * (row total) once the level-0 histogram knows the total.
 // Returns K; above = weight strictly above K's group.
-template <bool MASS>
+template <bool MASS, class A = SfAll>
 __device__ unsigned sf_descend(const float* __restrict__ lb, int V, float xmax,
                                float invT, u64 target, float pfrac,
-                               SfShared& sh, u64& above_out) {
+                               SfShared& sh, u64& above_out,
+                               const A& allow = A()) {
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   u64* myh = sh.hist + wid * SF_BINS;
   unsigned prefix = 0;
@@ -155,7 +169,7 @@ __device__ unsigned sf_descend(const float* __restrict__ lb, int V, float xmax,
     __syncthreads();
     int cur = 0;
     u64 acc = 0;
-    sf_foreach(lb, V, [&](float x, int) {
+    sf_foreach(lb, V, allow, [&](float x, int) {
       const unsigned key = sf_key(x);
       if (level > 0 && ((key ^ prefix) >> (shift + 8)) != 0) return;
       const int bin = (int)((key >> shift) & (SF_BINS - 1));
@@ -256,14 +270,16 @@ struct SfRow {
 // Pre-pass and phase 1: row statistics, then the threshold logit tau of the
 // kept set {v : logit_v >= tau} after top-k then top-p.  Whole block; every
 // thread returns the same SfRow.
+template <class A = SfAll>
 __device__ __forceinline__ SfRow sf_threshold(const float* __restrict__ lb,
                                               int V, float T, int k, float p,
-                                              SfShared& sh) {
+                                              SfShared& sh,
+                                              const A& allow = A()) {
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   // ---- pre-pass: row max, smallest finite logit, number of finite logits
   float xmax = -INFINITY, xmin = INFINITY;
   int nfin = 0;
-  sf_foreach(lb, V, [&](float x, int) {
+  sf_foreach(lb, V, allow, [&](float x, int) {
     xmax = fmaxf(xmax, x);
     if (x > -INFINITY) { xmin = fminf(xmin, x); ++nfin; }
   });
@@ -297,13 +313,13 @@ __device__ __forceinline__ SfRow sf_threshold(const float* __restrict__ lb,
     if (k_on) {
       u64 cgt;
       const unsigned key_k = sf_descend<false>(lb, V, xmax, invT, (u64)k, -1.f,
-                                               sh, cgt);
+                                               sh, cgt, allow);
       tau = sf_unkey(key_k);
       if (p_on) {
         // M_k: mass of exactly the k best (ties at the k-th value weigh the
         // same, so which of them count is immaterial)
         u64 part = 0;
-        sf_foreach(lb, V, [&](float x, int) {
+        sf_foreach(lb, V, allow, [&](float x, int) {
           if (sf_key(x) > key_k) part += sf_mass(x, xmax, invT);
         });
         const u64 mk = sf_block_sum64(part, sh) +
@@ -314,7 +330,8 @@ __device__ __forceinline__ SfRow sf_threshold(const float* __restrict__ lb,
     if (p_on) {
       u64 unused;
       const unsigned key_p = sf_descend<true>(
-          lb, V, xmax, invT, target, k_on ? -1.f : fmaxf(p, 0.f), sh, unused);
+          lb, V, xmax, invT, target, k_on ? -1.f : fmaxf(p, 0.f), sh, unused,
+          allow);
       tau = sf_unkey(key_p);
     }
   }
@@ -325,10 +342,12 @@ __device__ __forceinline__ SfRow sf_threshold(const float* __restrict__ lb,
 // hashed from (seed, step, v).  Whole block; the token is valid on thread 0
 // only, and nothing follows the function's one block barrier but thread 0's
 // scan of the per-wave winners.
+template <class A = SfAll>
 __device__ __forceinline__ long sf_gumbel_argmax(const float* __restrict__ lb,
                                                  int V, const SfRow& r,
                                                  long seed, int step,
-                                                 SfShared& sh) {
+                                                 SfShared& sh,
+                                                 const A& allow = A()) {
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   const float xmax = r.xmax, invT = r.invT, tau = r.tau;
   const bool greedy = r.greedy;
@@ -337,7 +356,7 @@ __device__ __forceinline__ long sf_gumbel_argmax(const float* __restrict__ lb,
   const unsigned k0 = (unsigned)rk, k1 = (unsigned)(rk >> 32);
   float best = -INFINITY;
   int besti = 0x7fffffff;
-  sf_foreach(lb, V, [&](float x, int v) {
+  sf_foreach(lb, V, allow, [&](float x, int v) {
     if (!(x >= tau)) return;
     float sc = x;
     if (!greedy) {
@@ -438,7 +457,171 @@ __global__ __launch_bounds__(SF_THREADS) void sample_slots_kernel(
   }
 }
 
+// ---- grammar-constrained sampling
+//
+// A row in automaton state s (0 <= s < N) with `left` tokens remaining may
+// pick token v iff v < Vc = min(V, Vt), bit v of mask[s] is set and
+// dist[next[s, v]] <= left - 1.  The allowed set is built ONCE per row as a
+// bitset in LDS: every mask word is loaded once (one word per 32 tokens),
+// and only when the budget can bind (left - 1 < max_dist, block-uniform)
+// does a second sweep read next[s, .] (one contiguous int16 row) and dist
+// through it to clear tokens that could no longer finish in time.  The
+// passes of sf_threshold / sf_gumbel_argmax then see -inf for every other
+// token and read only the first Vc logits of the row.
+#define SC_MAX_WORDS 2048  // bitset words in LDS: Vt <= 65536
+
+struct ScAllowed {
+  const unsigned* bits;
+  __device__ __forceinline__ float operator()(float x, int v) const {
+    return ((bits[v >> 5] >> (v & 31)) & 1u) ? x : -INFINITY;
+  }
+};
+
+// Whole block.  s is a valid state; ends on a block barrier.
+__device__ __forceinline__ void sc_build_allowed(
+    unsigned* bits, const int* __restrict__ mask,
+    const short* __restrict__ next, const short* __restrict__ dist, int s,
+    int left, int Vc, int Vt, int N, int W, int max_dist) {
+  const int nw = (Vc + 31) >> 5;
+  for (int w = threadIdx.x; w < nw; w += SF_THREADS) {
+    unsigned m = (unsigned)mask[(long)s * W + w];
+    const int rem = Vc - 32 * w;  // >= 1
+    if (rem < 32) m &= (1u << rem) - 1u;
+    bits[w] = m;
+  }
+  __syncthreads();
+  if (left - 1 < max_dist) {
+    const short* nr = next + (long)s * Vt;
+    for (int v = threadIdx.x; v < Vc; v += SF_THREADS) {
+      const unsigned bit = 1u << (v & 31);
+      if (bits[v >> 5] & bit) {
+        const int nx = nr[v];
+        const bool ok = nx >= 0 && nx < N && (int)dist[nx] <= left - 1;
+        if (!ok) atomicAnd(&bits[v >> 5], ~bit);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Thread 0, after the last barrier: the token of a constrained row.  A row
+// whose allowed logits are all -inf / NaN takes the lowest allowed index
+// (the unconstrained fallthrough, token 0, is PAD).  Returns -1 when
+// nothing is allowed at all.
+__device__ __forceinline__ long sc_finish(const unsigned* bits, int Vc,
+                                          const SfRow& r, long tok) {
+  if (r.xmax == -INFINITY) {
+    tok = -1;
+    const int nw = (Vc + 31) >> 5;
+    for (int w = 0; w < nw; ++w)
+      if (bits[w]) { tok = 32 * w + __ffs((int)bits[w]) - 1; break; }
+  }
+  return tok;
+}
+
+// SLOTS=false: row b samples with (temperature, top_k, top_p, seed, step,
+// state, left)[b] and writes tok[b].  SLOTS=true: sample_slots_kernel's
+// addressing (slot / active, arrays are [S], step advanced).  A row whose
+// state is outside [0, N) is unconstrained: sample_filtered's arithmetic
+// over all V logits, state and left untouched.  Otherwise state[i] =
+// next[state, tok] and left[i] -= 1.  Every early return is block-uniform.
+template <bool SLOTS>
+__global__ __launch_bounds__(SF_THREADS) void sample_constrained_kernel(
+    const float* __restrict__ logits, const int* __restrict__ slot,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, const long* __restrict__ seed,
+    int* __restrict__ step, const unsigned char* __restrict__ active,
+    long* __restrict__ tok, int* __restrict__ state, int* __restrict__ left,
+    const short* __restrict__ next, const int* __restrict__ mask,
+    const short* __restrict__ dist, int S, int V, int Vt, int N, int W,
+    int max_dist) {
+  __shared__ SfShared sh;
+  __shared__ unsigned bits[SC_MAX_WORDS];
+  const long row = blockIdx.x;
+  int s = (int)row;
+  if (SLOTS) {
+    s = slot ? slot[row] : (int)row;
+    if (s < 0 || s >= S) return;
+    if (active && active[s] == 0) return;
+  }
+  const int st = step[s];
+  const int q = state[s];
+  const float* lb = logits + row * (long)V;
+  const float T = temperature[s];
+  const int k = top_k[s];
+  const float p = top_p[s];
+  const long sd = seed[s];
+  if (q < 0 || q >= N) {
+    const SfRow r = sf_threshold(lb, V, T, k, p, sh);
+    const long t = sf_gumbel_argmax(lb, V, r, sd, st, sh);
+    if (threadIdx.x == 0) {
+      tok[s] = t;
+      if (SLOTS) step[s] = st + 1;
+    }
+    return;
+  }
+  const int lf = left[s];
+  const int Vc = min(V, Vt);
+  sc_build_allowed(bits, mask, next, dist, q, lf, Vc, Vt, N, W, max_dist);
+  const ScAllowed allow{bits};
+  const SfRow r = sf_threshold(lb, Vc, T, k, p, sh, allow);
+  long t = sf_gumbel_argmax(lb, Vc, r, sd, st, sh, allow);
+  if (threadIdx.x == 0) {
+    t = sc_finish(bits, Vc, r, t);
+    // nothing allowed (a budget the caller did not establish): PAD, and the
+    // row keeps its state
+    const bool ok = t >= 0 && t < Vc && ((bits[t >> 5] >> (t & 31)) & 1u);
+    tok[s] = ok ? t : 0;
+    if (ok) {
+      state[s] = next[(long)q * Vt + t];
+      left[s] = lf - 1;
+    }
+    if (SLOTS) step[s] = st + 1;
+  }
+}
+
 extern "C" {
+
+static bool sc_tables_ok(int V, int Vt, int N, int W, int max_dist) {
+  return V > 0 && Vt > 0 && N >= 1 && N <= 32767 && W == (Vt + 31) / 32 &&
+         W <= SC_MAX_WORDS && max_dist >= 0;
+}
+
+hipError_t sentio_sample_constrained(
+    const float* logits, const float* temperature, const int* top_k,
+    const float* top_p, const long* seed, const int* step, int* state,
+    int* left, const short* next, const int* mask, const short* dist,
+    long* tok, long B, int V, int Vt, int N, int W, int max_dist,
+    hipStream_t stream) {
+  if (B <= 0 || B > 0x7fffffffL || !sc_tables_ok(V, Vt, N, W, max_dist))
+    return hipErrorInvalidValue;
+  // SLOTS=false never writes step
+  hipLaunchKernelGGL((sample_constrained_kernel<false>), dim3((unsigned)B),
+                     dim3(SF_THREADS), 0, stream, logits, (const int*)nullptr,
+                     temperature, top_k, top_p, seed, const_cast<int*>(step),
+                     (const unsigned char*)nullptr, tok, state, left, next,
+                     mask, dist, (int)B, V, Vt, N, W, max_dist);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_sample_slots_constrained(
+    const float* logits, const int* slot, const float* temperature,
+    const int* top_k, const float* top_p, const long* seed, int* step,
+    const unsigned char* active, long* tok, int* state, int* left,
+    const short* next, const int* mask, const short* dist, long R, int S,
+    int V, int Vt, int N, int W, int max_dist, hipStream_t stream) {
+  if (R <= 0 || S <= 0 || R > 0x7fffffffL ||
+      !sc_tables_ok(V, Vt, N, W, max_dist))
+    return hipErrorInvalidValue;
+  if (!slot && R != S) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((sample_constrained_kernel<true>), dim3((unsigned)R),
+                     dim3(SF_THREADS), 0, stream, logits, slot, temperature,
+                     top_k, top_p, seed, step, active, tok, state, left, next,
+                     mask, dist, S, V, Vt, N, W, max_dist);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 hipError_t sentio_sample_support(const float* logits, const float* temperature,
                                  const int* top_k, const float* top_p,

@@ -77,6 +77,28 @@ hipError_t sentio_sample_slots(const float* logits, const int* slot,
                                const float* top_p, const long* seed, int* step,
                                const unsigned char* active, long* tok, long R,
                                int S, int V, hipStream_t stream);
+// grammar-constrained sample_filtered.  state / left are int32 [B], in/out;
+// next int16 [N, Vt], mask int32 [N, W] with W == ceil(Vt/32), dist int16
+// [N]; max_dist >= every dist entry.  A row with state in [0, N) draws only
+// from v < min(V, Vt) with mask bit v set and dist[next[state, v]] <=
+// left - 1, then state = next[state, tok], left -= 1; any other state is
+// sampled unconstrained and keeps state and left.  Dims are (B, V, Vt, N,
+// W, max_dist); hipErrorInvalidValue unless 1 <= N <= 32767, W matches Vt
+// and W <= 2048
+hipError_t sentio_sample_constrained(
+    const float* logits, const float* temperature, const int* top_k,
+    const float* top_p, const long* seed, const int* step, int* state,
+    int* left, const short* next, const int* mask, const short* dist,
+    long* tok, long B, int V, int Vt, int N, int W, int max_dist,
+    hipStream_t stream);
+// sentio_sample_slots with per-slot state / left [S]; the tables follow
+// them, dims are (R, S, V, Vt, N, W, max_dist)
+hipError_t sentio_sample_slots_constrained(
+    const float* logits, const int* slot, const float* temperature,
+    const int* top_k, const float* top_p, const long* seed, int* step,
+    const unsigned char* active, long* tok, int* state, int* left,
+    const short* next, const int* mask, const short* dist, long R, int S,
+    int V, int Vt, int N, int W, int max_dist, hipStream_t stream);
 
 // ---- retrieval.hip
 // index matrix first, queries second; dims are (N, D, B)

@@ -327,6 +327,90 @@ def sample_slots(logits: torch.Tensor, slot, temperature, top_k, top_p, seed,
         step[s] += 1
 
 
+def constrained_allowed(state: int, left: int, V: int, nxt: torch.Tensor,
+                        mask: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
+    """bool [V]: the tokens a row in automaton state `state` with `left`
+    tokens remaining may pick.  v is allowed iff v < min(V, Vt), bit v of
+    mask[state] is set and dist[next[state, v]] <= left - 1."""
+    Vt = nxt.shape[1]
+    Vc = min(V, Vt)
+    v = torch.arange(Vc)
+    words = mask[state].to(torch.int64)[v >> 5]
+    bit = ((words >> (v & 31)) & 1).bool()
+    to = nxt[state, :Vc].to(torch.int64)
+    ok = bit & (to >= 0)
+    ok &= dist.to(torch.int64)[to.clamp_min(0)] <= int(left) - 1
+    out = torch.zeros(V, dtype=torch.bool)
+    out[:Vc] = ok
+    return out
+
+
+def _constrained_row(row, t, k, p, sd, st, state: int, left: int, nxt, mask,
+                     dist):
+    """One row of sample_constrained -> (token, new state, new left)."""
+    N = nxt.shape[0]
+    if state < 0 or state >= N:
+        return int(sample_filtered(row[None], t, k, p, sd, st)[0]), state, left
+    ok = constrained_allowed(state, left, row.shape[0], nxt, mask, dist)
+    if not bool(ok.any()):
+        return 0, state, left
+    x = row.detach().cpu().float()
+    masked = torch.where(ok, x, torch.full_like(x, -math.inf))
+    finite = torch.isfinite(masked) | (masked == math.inf)
+    if not bool(finite.any()):
+        tok = int(torch.nonzero(ok)[0])      # lowest allowed index
+    else:
+        tok = int(sample_filtered(masked[None], t, k, p, sd, st)[0])
+    return tok, int(nxt[state, tok]), left - 1
+
+
+def sample_constrained(logits, temperature, top_k, top_p, seed, step,
+                       state: torch.Tensor, left: torch.Tensor, nxt, mask,
+                       dist) -> torch.Tensor:
+    """Grammar-constrained sample_filtered, in place on `state` and `left`
+    (int32 [B]).  Disallowed logits (constrained_allowed) count as -inf, the
+    rest is sample_filtered; then state = next[state, tok], left -= 1.  A
+    row whose allowed logits are all -inf / NaN takes the lowest allowed
+    index.  A row with state outside [0, N) is sampled by sample_filtered
+    over the whole row and keeps state and left."""
+    x = logits.detach().cpu().float()
+    B = x.shape[0]
+    t, k, p = _row_params(B, temperature, top_k, top_p)
+    sd = torch.as_tensor(seed).detach().cpu().to(torch.int64).flatten()
+    st = torch.as_tensor(step).detach().cpu().to(torch.int64).flatten()
+    sd = sd.expand(B) if sd.numel() == 1 else sd
+    st = st.expand(B) if st.numel() == 1 else st
+    out = torch.empty(B, dtype=torch.int64)
+    for b in range(B):
+        tok, ns, nl = _constrained_row(
+            x[b], t[b:b + 1], k[b:b + 1], p[b:b + 1], sd[b:b + 1],
+            st[b:b + 1], int(state[b]), int(left[b]), nxt, mask, dist)
+        out[b] = tok
+        state[b] = ns
+        left[b] = nl
+    return out
+
+
+def sample_slots_constrained(logits, slot, temperature, top_k, top_p, seed,
+                             step, active, tok, state, left, nxt, mask,
+                             dist) -> None:
+    """sample_slots with per-slot automaton state: slot s samples through
+    sample_constrained with (state[s], left[s]), all in place."""
+    R, S = logits.shape[0], tok.shape[0]
+    slots = list(range(R)) if slot is None \
+        else [int(s) for s in torch.as_tensor(slot).flatten().tolist()]
+    if len(slots) != R:
+        raise ValueError(f"{len(slots)} slots for {R} logits rows")
+    for r, s in enumerate(slots):
+        if s < 0 or s >= S or (active is not None and int(active[s]) == 0):
+            continue
+        tok[s] = sample_constrained(
+            logits[r:r + 1], temperature[s:s + 1], top_k[s:s + 1],
+            top_p[s:s + 1], seed[s:s + 1], step[s:s + 1], state[s:s + 1],
+            left[s:s + 1], nxt, mask, dist)[0]
+        step[s] += 1
+
+
 def decode_qkv_prep(
     qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor

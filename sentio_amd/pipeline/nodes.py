@@ -148,6 +148,8 @@ def create_generator_node(generator, mode: str = "balanced",
             sampling["top_k"] = int(meta["sampling_top_k"])
         if isinstance(meta.get("seed"), int):
             sampling["seed"] = int(meta["seed"])
+        if meta.get("grammar") is not None:     # response_format
+            sampling["grammar"] = meta["grammar"]
         history = state.get("metadata", {}).get("history") or []
         hist_txt = "".join(
             f"{turn.get('role', 'user')}: {turn.get('content', '')}\n"

@@ -55,18 +55,39 @@ def _repair(s: str) -> str:
 
 
 class AnswerVerifier:
-    def __init__(self, generator, max_tokens: int = 512):
+    def __init__(self, generator, max_tokens: int = 512,
+                 constrained: bool = False):
         self.generator = generator
         self.builder = PromptBuilder()
         self.max_tokens = max_tokens
+        # constrained: decode under VERDICT_GRAMMAR, so the reply always
+        # parses; off (the default): the generator is called as before
+        self.constrained = bool(constrained)
+
+    def _constrained_kwargs(self) -> dict:
+        """The grammar and a token budget of at least the grammar's shortest
+        completion under the generator's tokenizer."""
+        from sentio_amd.engines.grammar import VERDICT_GRAMMAR
+
+        budget = self.max_tokens
+        tok = getattr(self.generator, "tokenizer", None)
+        if tok is not None:
+            tb = VERDICT_GRAMMAR.token_tables(tok)
+            budget = max(budget, int(tb.dist[tb.start]))
+        return {"max_new_tokens": budget, "grammar": VERDICT_GRAMMAR}
 
     def verify(self, query: str, context: str, answer: str) -> VerifyResult:
         prompt = self.builder.build_verify_prompt(query=query, context=context,
                                                   answer=answer)
         try:
-            text = self.generator.generate(
-                [prompt], max_new_tokens=self.max_tokens, temperature=0.0
-            )[0]
+            if self.constrained:
+                text = self.generator.generate(
+                    [prompt], temperature=0.0, **self._constrained_kwargs()
+                )[0]
+            else:
+                text = self.generator.generate(
+                    [prompt], max_new_tokens=self.max_tokens, temperature=0.0
+                )[0]
             return self._normalize(extract_json_dict(text))
         except Exception as exc:
             logger.warning("verify() failed: %s", exc)

@@ -67,6 +67,9 @@ class ChatRequest(BaseModel):
     top_p: float | None = Field(default=None, gt=0.0, le=1.0)
     sampling_top_k: int | None = Field(default=None, ge=0)   # 0 = off
     seed: int | None = Field(default=None, ge=0)
+    # constrained decoding: {"type": "regex", "pattern": ...} or
+    # {"type": "json_object", "fields": [...]}
+    response_format: dict | None = None
 
     @field_validator("question")
     @classmethod
@@ -230,13 +233,48 @@ def create_app(settings: Settings | None = None,
     async def health_live():
         return {"status": "alive"}
 
+    def _response_grammar(req: ChatRequest):
+        """The request's response_format as a grammar registered with the
+        generator (so a full grammar table shows here, not inside the
+        pipeline); 422 with the compiler's message when it is unsupported,
+        too large, or cannot finish within LLM_MAX_TOKENS, 503 when the
+        process has no room for another grammar.  Runs in the worker
+        pool."""
+        fmt = req.response_format
+        if fmt is None and getattr(s, "gen_regex", ""):
+            fmt = {"type": "regex", "pattern": s.gen_regex}   # run --regex
+        if fmt is None:
+            return None
+        from sentio_amd.serving.handlers import (GrammarBudgetError,
+                                                 compile_response_format)
+
+        generator = container.generator()
+        try:
+            grammar = compile_response_format(
+                fmt, getattr(generator, "tokenizer", None), s.llm_max_tokens)
+        except GrammarBudgetError as exc:
+            raise HTTPException(status_code=503, detail=str(exc))
+        except ValueError as exc:
+            raise HTTPException(status_code=422, detail=str(exc))
+        register = getattr(generator, "register_grammar", None)
+        if register is not None:
+            try:
+                register(grammar)
+            except ValueError as exc:      # the engine's table is full
+                raise HTTPException(status_code=503, detail=str(exc))
+        return grammar
+
     @app.post("/chat", response_model=ChatResponse)
     async def chat(req: ChatRequest):
         with metrics_collector.track_request("/chat"):
             t0 = time.perf_counter()
+            # compile, table build and registration are pure Python and may
+            # take a good part of a second: never on the event loop
+            grammar = await _run_sync(_response_grammar, req)
             result = await _run_sync(chat_handler.process, req.question,
                                      req.top_k, req.temperature, req.history,
-                                     req.top_p, req.sampling_top_k, req.seed)
+                                     req.top_p, req.sampling_top_k, req.seed,
+                                     grammar)
             performance_monitor.record_value(
                 "chat_latency_ms", (time.perf_counter() - t0) * 1e3)
             return result
@@ -246,6 +284,7 @@ def create_app(settings: Settings | None = None,
         """SSE token streaming (reference streamed via OpenAI SSE pass-through;
         here tokens stream straight off the decode loop)."""
         container.initialize_all()
+        grammar = await _run_sync(_response_grammar, req)
 
         def gen():
             from sentio_amd.pipeline.context import prepare_context
@@ -275,6 +314,8 @@ def create_app(settings: Settings | None = None,
                                         req.seed)
             if "sampling_top_k" in sampling:
                 sampling["top_k"] = sampling.pop("sampling_top_k")
+            if grammar is not None:
+                sampling["grammar"] = grammar
             for delta in container.generator_frontend().stream(
                     prompt, max_new_tokens=s.llm_max_tokens,
                     temperature=req.temperature or 0.3, **sampling):

@@ -67,28 +67,37 @@ class _SampledItem(_Item):
     top_k: int = 0
     top_p: float = 1.0
     seed: int | None = None
+    # constrained decoding: the engine's GrammarHandle (or a Grammar for a
+    # generator that resolves it itself); None for a free-text request
+    grammar: Any = None
 
     @property
     def sampling_kwargs(self) -> dict:
-        return {"top_k": self.top_k, "top_p": self.top_p, "seed": self.seed}
+        kw = {"top_k": self.top_k, "top_p": self.top_p, "seed": self.seed}
+        if self.grammar is not None:
+            kw["grammar"] = self.grammar
+        return kw
 
     @property
     def group_key(self) -> tuple:
         # a wave draws prompt i with seed + i: a seeded request must sit at
         # row 0 of its own wave to reproduce, so it never shares one
+        # a wave shares one grammar: the handle (by identity) is in the key
         return (self.temperature, self.max_new_tokens, self.stop_on_eos,
                 self.top_k, self.top_p, self.seed,
-                id(self) if self.seed is not None else None)
+                id(self) if self.seed is not None else None,
+                id(self.grammar) if self.grammar is not None else None)
 
 
 def _make_item(prompt: str, max_new_tokens: int, temperature: float,
                stop_on_eos: bool, stream_q=None, top_k: int = 0,
-               top_p: float = 1.0, seed: int | None = None) -> _Item:
+               top_p: float = 1.0, seed: int | None = None,
+               grammar=None) -> _Item:
     top_k, top_p = int(top_k or 0), float(top_p)
-    if top_k > 0 or top_p < 1.0 or seed is not None:
+    if top_k > 0 or top_p < 1.0 or seed is not None or grammar is not None:
         return _SampledItem(prompt, max_new_tokens, float(temperature),
                             stop_on_eos, stream_q=stream_q, top_k=top_k,
-                            top_p=top_p, seed=seed)
+                            top_p=top_p, seed=seed, grammar=grammar)
     return _Item(prompt, max_new_tokens, float(temperature), stop_on_eos,
                  stream_q=stream_q)
 
@@ -100,12 +109,35 @@ def _slot_params(item: _Item):
 
     return SamplingParams(item.temperature, getattr(item, "top_k", 0),
                           getattr(item, "top_p", 1.0),
-                          getattr(item, "seed", None))
+                          getattr(item, "seed", None),
+                          getattr(item, "grammar", None))
+
+
+def _resolve_grammar(generator, grammar, max_new_tokens: int):
+    """A request's grammar -> the engine's handle, with the budget checked
+    in the caller's thread (ValueError before the request is queued).  A
+    generator without grammar tables (mock engines) gets it unchanged."""
+    if grammar is None:
+        return None
+    resolve = getattr(generator, "resolve_grammar", None)
+    if resolve is None:
+        return grammar
+    handle = resolve(grammar)
+    # the budget the engine will really grant: generate() clamps to
+    # max_seq - 9, and so does the slot loop at worst (admission leaves a
+    # prompt at least 8 tokens, and decode stops at the cache end) -- so the
+    # loop thread's admit() can never find a budget too small
+    cap = getattr(generator, "max_seq", None)
+    budget = int(max_new_tokens) if cap is None \
+        else max(1, min(int(max_new_tokens), int(cap) - 9))
+    generator.check_grammar_budget(handle, budget)
+    return handle
 
 
 def _sampling_only(kwargs: dict) -> dict:
-    """The nucleus-sampling keywords of a frontend call (top_k / top_p /
-    seed) that switch a filter on; {} for a default request."""
+    """The sampling keywords of a frontend call (top_k / top_p / seed /
+    grammar) that take a request off the default path; {} for a default
+    request."""
     out = {}
     if int(kwargs.get("top_k") or 0) > 0:
         out["top_k"] = int(kwargs["top_k"])
@@ -113,6 +145,8 @@ def _sampling_only(kwargs: dict) -> dict:
         out["top_p"] = float(kwargs["top_p"])
     if kwargs.get("seed") is not None:
         out["seed"] = int(kwargs["seed"])
+    if kwargs.get("grammar") is not None:
+        out["grammar"] = kwargs["grammar"]
     return out
 
 
@@ -132,26 +166,30 @@ class DynamicBatcher:
     def generate(self, prompt: str, max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
                  timeout_s: float = 300.0, top_k: int = 0,
-                 top_p: float = 1.0, seed: int | None = None) -> str:
+                 top_p: float = 1.0, seed: int | None = None,
+                 grammar=None) -> str:
+        grammar = _resolve_grammar(self.generator, grammar, max_new_tokens)
         self.start()
         item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
-                          top_k=top_k, top_p=top_p, seed=seed)
+                          top_k=top_k, top_p=top_p, seed=seed,
+                          grammar=grammar)
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
 
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
                         temperature: float = 0.3, timeout_s: float = 300.0,
                         top_k: int = 0, top_p: float = 1.0,
-                        seed: int | None = None):
+                        seed: int | None = None, grammar=None):
         """Yield text deltas token-by-token.  The request JOINS batched
         decode (continuous-batching-lite: it occupies a batch slot and its
         token ids stream out per decode step); concurrent non-stream chat
         requests coalesce into the same engine batches, so neither starves
         the other."""
+        grammar = _resolve_grammar(self.generator, grammar, max_new_tokens)
         self.start()
         item = _make_item(prompt, max_new_tokens, temperature, True,
                           stream_q=queue.Queue(), top_k=top_k, top_p=top_p,
-                          seed=seed)
+                          seed=seed, grammar=grammar)
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
 
@@ -324,13 +362,14 @@ class ContinuousBatcher:
 
     # ----- caller side -----
     def _item(self, prompt, max_new_tokens, temperature, stop_on_eos,
-              stream_q, top_k, top_p, seed) -> _Item:
+              stream_q, top_k, top_p, seed, grammar=None) -> _Item:
+        grammar = _resolve_grammar(self.generator, grammar, max_new_tokens)
         item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
                           stream_q=stream_q, top_k=top_k, top_p=top_p,
-                          seed=seed)
+                          seed=seed, grammar=grammar)
         if isinstance(item, _SampledItem) and not self.slot_sampling:
             raise ValueError(
-                "top_k / top_p / seed need ContinuousBatcher("
+                "top_k / top_p / seed / grammar need ContinuousBatcher("
                 "slot_sampling=True): the default slot loop samples with "
                 "per-row temperature only")
         return item
@@ -338,9 +377,10 @@ class ContinuousBatcher:
     def generate(self, prompt: str, max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,
                  timeout_s: float = 300.0, top_k: int = 0,
-                 top_p: float = 1.0, seed: int | None = None) -> str:
+                 top_p: float = 1.0, seed: int | None = None,
+                 grammar=None) -> str:
         item = self._item(prompt, max_new_tokens, temperature, stop_on_eos,
-                          None, top_k, top_p, seed)
+                          None, top_k, top_p, seed, grammar)
         self.start()
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
@@ -348,9 +388,9 @@ class ContinuousBatcher:
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
                         temperature: float = 0.3, timeout_s: float = 300.0,
                         top_k: int = 0, top_p: float = 1.0,
-                        seed: int | None = None):
+                        seed: int | None = None, grammar=None):
         item = self._item(prompt, max_new_tokens, temperature, True,
-                          queue.Queue(), top_k, top_p, seed)
+                          queue.Queue(), top_k, top_p, seed, grammar)
         self.start()
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
@@ -569,9 +609,14 @@ class ContinuousBatcher:
                             tok0 = gen.sample_rows(logits,
                                                    t_adm).cpu().tolist()
                         else:
-                            # the step-0 draw, scattered into cur[rows]
-                            sampler.admit(rows, [_slot_params(it)
-                                                 for it in items])
+                            # the step-0 draw, scattered into cur[rows];
+                            # a constrained slot's budget is the number of
+                            # tokens the loop will really feed it
+                            sampler.admit(
+                                rows, [_slot_params(it) for it in items],
+                                [min(it.max_new_tokens,
+                                     max(1, sess.cache.max_seq - n - 1))
+                                 for it, n in zip(items, lens_host)])
                             sampler.sample(logits, cur, rows=rows)
                             cur_host = cur.cpu().tolist()
                             tok0 = [cur_host[r] for r in rows]
@@ -666,7 +711,9 @@ class ContinuousGenerator:
     decodes.
 
     slot_sampling=True: the loop samples per slot (ops.sample_slots), and
-    single-prompt requests that set top_k and/or top_p and NO seed join it.
+    single-prompt requests that set top_k and/or top_p and NO seed join it;
+    so does a request with a grammar (each slot carries its own automaton
+    state; a wave shares one grammar, so the handle is part of the wave key).
     Seeded requests stay on the wave path in both modes: a seed promises
     the same answer whatever else shares the engine, and in the slot loop a
     request's logits come from a different row of a shared batch on each

@@ -151,7 +151,9 @@ class ServiceContainer:
 
     def verifier(self):
         return self._get("verifier", lambda: AnswerVerifier(
-            self.generator(), max_tokens=self.settings.verifier_max_tokens))
+            self.generator(), max_tokens=self.settings.verifier_max_tokens,
+            constrained=getattr(self.settings, "verifier_constrained",
+                                False)))
 
     def pipeline(self) -> RagPipeline:
         def make():

@@ -5,6 +5,7 @@ cached-response → template → apology, plus health probes."""
 from __future__ import annotations
 
 import logging
+import threading
 import time
 import uuid
 from typing import Any
@@ -40,6 +41,85 @@ def resolve_sampling(settings, top_p: float | None = None,
     return out
 
 
+# pattern -> Grammar, or the ValueError of a pattern that did not compile
+# (a hostile pattern costs its compile budget once, not once per request)
+_grammar_cache: dict[str, Any] = {}
+_grammar_cache_lock = threading.Lock()
+_GRAMMAR_CACHE_MAX = 64
+# An engine's grammar table is append-only (32766 states for the life of the
+# process), so the patterns that arrive through the API share a budget that
+# leaves half of it to the service's own grammars.
+API_GRAMMAR_STATE_BUDGET = 16384
+_api_patterns: dict[str, int] = {}          # pattern -> table states
+
+
+class GrammarBudgetError(ValueError):
+    """The process has no room for another API grammar."""
+
+
+def compile_response_format(fmt: dict | None, tokenizer=None,
+                            max_new_tokens: int | None = None):
+    """A request's `response_format` -> Grammar (None for None).
+    {"type": "regex", "pattern": ...} or {"type": "json_object", "fields":
+    [...]} (see engines/grammar.py).  Compiled grammars are cached per
+    process by pattern, failures included.  ValueError, with the compiler's
+    message, for unsupported syntax, more than API_MAX_STATES automaton
+    states, a compile that exceeds its work or time budget
+    (API_COMPILE_SECONDS), or a grammar whose shortest completion does not
+    fit max_new_tokens; GrammarBudgetError once the distinct patterns seen
+    by this process hold API_GRAMMAR_STATE_BUDGET table states."""
+    if fmt is None:
+        return None
+    from sentio_amd.engines.grammar import (API_COMPILE_SECONDS,
+                                            API_MAX_STATES, Grammar,
+                                            json_object_regex)
+
+    if not isinstance(fmt, dict):
+        raise ValueError("response_format must be an object")
+    kind = fmt.get("type")
+    if kind == "regex":
+        pattern = fmt.get("pattern")
+        if not isinstance(pattern, str) or not pattern:
+            raise ValueError("response_format.pattern must be a string")
+        if len(pattern) > 4096:
+            raise ValueError("response_format.pattern is too long")
+    elif kind == "json_object":
+        pattern = json_object_regex(fmt.get("fields"))
+    else:
+        raise ValueError("response_format.type must be 'regex' or "
+                         "'json_object'")
+    with _grammar_cache_lock:
+        grammar = _grammar_cache.get(pattern)
+    if grammar is None:
+        try:
+            grammar = Grammar.from_regex(pattern, max_states=API_MAX_STATES,
+                                         seconds=API_COMPILE_SECONDS)
+        except ValueError as exc:
+            grammar = exc
+        with _grammar_cache_lock:
+            if len(_grammar_cache) >= _GRAMMAR_CACHE_MAX:
+                _grammar_cache.pop(next(iter(_grammar_cache)))
+            grammar = _grammar_cache.setdefault(pattern, grammar)
+    if isinstance(grammar, ValueError):
+        raise ValueError(str(grammar))
+    with _grammar_cache_lock:
+        if pattern not in _api_patterns:
+            used = sum(_api_patterns.values())
+            if used + grammar.n_states + 1 > API_GRAMMAR_STATE_BUDGET:
+                raise GrammarBudgetError(
+                    f"no room for another response_format grammar: {used} of "
+                    f"{API_GRAMMAR_STATE_BUDGET} states are in use")
+            _api_patterns[pattern] = grammar.n_states + 1
+    if tokenizer is not None and max_new_tokens is not None:
+        tb = grammar.token_tables(tokenizer)
+        if int(tb.dist[tb.start]) > int(max_new_tokens):
+            raise ValueError(
+                f"the shortest reply of this response_format takes "
+                f"{int(tb.dist[tb.start])} tokens, the limit is "
+                f"{int(max_new_tokens)}")
+    return grammar
+
+
 class ChatHandler:
     def __init__(self, container: ServiceContainer):
         self.container = container
@@ -50,11 +130,15 @@ class ChatHandler:
                 history: list[dict[str, str]] | None = None,
                 top_p: float | None = None,
                 sampling_top_k: int | None = None,
-                seed: int | None = None) -> dict[str, Any]:
+                seed: int | None = None,
+                grammar=None) -> dict[str, Any]:
         """top_k is the RETRIEVAL depth; sampling_top_k / top_p / seed are
-        the generator's sampling controls."""
+        the generator's sampling controls; grammar (a compiled
+        response_format) constrains the answer."""
         query_id = str(uuid.uuid4())
         meta: dict[str, Any] = {"query_id": query_id}
+        if grammar is not None:
+            meta["grammar"] = grammar
         meta.update(resolve_sampling(getattr(self.container, "settings", None), top_p,
                                      sampling_top_k, seed))
         if top_k is not None:
