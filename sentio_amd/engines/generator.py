@@ -11,7 +11,7 @@ Temperature-per-mode mirrors reference generator.py:262-267
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Callable, Iterator
 
 import torch
@@ -173,6 +173,7 @@ class _DecodeSession:
         self.static_logits = None
         self.use_graphs = use_graphs
         self.batch = batch
+        self._verify: dict = {}     # T -> (graph, static tokens, logits)
 
     def prefill(self, tokens: torch.Tensor,
                 lens: torch.Tensor | None = None) -> torch.Tensor:
@@ -241,6 +242,36 @@ class _DecodeSession:
             self.static_logits = model.decode_step(self.static_tok, self.cache)
         self.cache.seq_lens.copy_(saved)
 
+    def verify_step(self, toks: torch.Tensor) -> torch.Tensor:
+        """Transformer.verify_step over toks [batch, T]; captured per T the
+        way _capture does the one-token step (it leaves seq_lens alone, so
+        nothing needs restoring: the rows the warm-up writes sit at or above
+        seq_lens and are rewritten before anything attends to them)."""
+        model = self.engine.model
+        if not self.use_graphs:
+            return model.verify_step(toks, self.cache)
+        T = int(toks.shape[1])
+        ent = self._verify.get(T)
+        if ent is None:
+            static = torch.zeros(self.batch, T, dtype=torch.int64,
+                                 device=self.engine.device)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    model.verify_step(static, self.cache)
+            torch.cuda.current_stream().wait_stream(s)
+            graph = torch.cuda.CUDAGraph()
+            from sentio_amd.engines.graphed import capture_gc_guard
+
+            with capture_gc_guard(), \
+                    torch.cuda.graph(graph, capture_error_mode="relaxed"):
+                logits = model.verify_step(static, self.cache)
+            ent = self._verify[T] = (graph, static, logits)
+        ent[1].copy_(toks)
+        ent[0].replay()
+        return ent[2]
+
     def decode_step(self, tok: torch.Tensor) -> torch.Tensor:
         if not self.use_graphs:
             return self.engine.model.decode_step(tok.view(self.batch, 1),
@@ -255,14 +286,21 @@ class _DecodeSession:
 class GeneratorEngine:
     def __init__(self, model: str = "llama3-8b", device: str = "cpu",
                  dtype: str = "bf16", max_seq: int = 4096, seed: int = 303,
-                 tp=None, kv_cache_dtype: str = "bf16"):
+                 tp=None, kv_cache_dtype: str = "bf16", spec_tokens: int = 0):
         self.cfg = get_model_config(model)
+        # Prompt-lookup speculative decoding, off at 0: K = spec_tokens
+        # draft tokens per step, verified in one T = K + 1 token forward
+        # (generate / stream; calls it cannot serve take the one-token path)
+        self.spec_tokens = int(spec_tokens)
+        self.last_spec = {"steps": 0, "drafted": 0, "accepted": 0}
         # "fp8": session caches hold e4m3fn bytes (half the HBM and half the
         # bytes a decode step streams); prefill and the prefix store stay in
         # the model dtype.  Raises here for a model the FP8 kernel cannot
         # serve, not at the first step.
         self.kv_cache_dtype = check_kv_dtype(kv_cache_dtype, self.cfg)
         self.device = device
+        if self.spec_tokens:
+            self._check_spec_shape(self.spec_tokens)
         self.max_seq = min(max_seq, self.cfg.max_seq)
         self.tokenizer = get_tokenizer()
         self.model = Transformer(self.cfg, device=device, dtype=dtype,
@@ -430,6 +468,122 @@ class GeneratorEngine:
         """The current engine-wide ops.GrammarTables (None before the first
         registration)."""
         return self._grammar_tables
+
+    # ----- prompt-lookup speculative decoding -----
+    def _check_spec_shape(self, k: int) -> None:
+        g = self.cfg.n_heads // self.cfg.n_kv_heads
+        if not 1 <= k <= 7:
+            raise ValueError(f"speculative tokens must be in [0, 7], got {k}")
+        if self.cfg.head_dim not in (64, 128) and self.device != "cpu":
+            raise ValueError("speculative decoding needs head dim 64 or 128, "
+                             f"got {self.cfg.head_dim}")
+        if g * (k + 1) > 32:
+            raise ValueError(
+                f"speculative decoding serves (query heads per kv head) * "
+                f"(tokens + 1) <= 32, got {g} * {k + 1}")
+
+    def _resolve_spec(self, speculative: int | None, grammar,
+                      on_token=None) -> int:
+        """Draft tokens per step for one call.  An explicit speculative > 0
+        the call cannot be served with raises ValueError; the engine default
+        gives way to the one-token path instead."""
+        k = self.spec_tokens if speculative is None else int(speculative)
+        if k <= 0:
+            return 0
+        why = None
+        if grammar is not None:
+            why = "a grammar (the automaton advances token by token)"
+        elif self.kv_cache_dtype == "fp8":
+            why = "kv_cache_dtype='fp8'"
+        elif self.model.tp.enabled:
+            why = "tensor parallelism"
+        elif on_token is not None:
+            why = "an on_token callback"
+        if why is None:
+            self._check_spec_shape(k)
+            return k
+        if speculative is None:
+            return 0
+        raise ValueError(f"speculative decoding does not combine with {why}")
+
+    def _spec_state(self, sess, hist_rows: list[list[int]], cur: torch.Tensor,
+                    max_new: int) -> dict:
+        """Device state of one speculative loop: hist holds each row's full
+        token sequence (prompt, then everything emitted, `cur` included)."""
+        dev = self.device
+        B = len(hist_rows)
+        L = max(len(r) for r in hist_rows) + max_new + 1
+        hist = torch.tensor([r + [0] * (L - len(r)) for r in hist_rows],
+                            dtype=torch.int64, device=dev)
+        hist_len = torch.tensor([len(r) for r in hist_rows],
+                                dtype=torch.int32, device=dev)
+        cur = cur.to(torch.int64).contiguous().clone()
+        hist[torch.arange(B, device=dev), hist_len.long()] = cur
+        hist_len += 1
+        out_buf = torch.zeros(B, max_new, dtype=torch.int64, device=dev)
+        out_buf[:, 0] = cur
+        out_len = torch.ones(B, dtype=torch.int32, device=dev)
+        smax = sess.cache.max_seq
+        room = torch.minimum(max_new - 1 - out_len,
+                             smax - 1 - sess.cache.seq_lens).to(torch.int32)
+        return {"hist": hist, "hist_len": hist_len, "cur": cur,
+                "out_buf": out_buf, "out_len": out_len, "room": room,
+                "stats": torch.zeros(B, 2, dtype=torch.int32, device=dev),
+                "max_new": max_new, "smax": smax}
+
+    def _spec_step(self, sess, st: dict, K: int, sample) -> None:
+        """One iteration: draft, verify, sample the B*T rows, accept.  All
+        on the device; st is updated in place."""
+        draft, n_draft = ops.ngram_draft(st["hist"], st["hist_len"],
+                                         st["room"], K)
+        toks = torch.cat([st["cur"].unsqueeze(1), draft], dim=1)
+        logits = sess.verify_step(toks)
+        sampled = sample(logits, st["out_len"]).view(-1, K + 1).contiguous()
+        ops.spec_accept(sampled, draft, n_draft, st["out_buf"], st["out_len"],
+                        st["max_new"], st["hist"], st["hist_len"],
+                        sess.cache.seq_lens, st["cur"], st["stats"],
+                        st["room"], st["smax"])
+
+    def _spec_sampler(self, sampling: SamplingParams | None,
+                      temperature: float, batch: int, T: int):
+        """sample(logits [B*T, V], out_len) for the verify rows.  Default
+        parameters: ops.sample_token over all rows.  Otherwise
+        ops.sample_filtered with step = out_len[b] + t, the step the
+        one-token loop would draw output token out_len[b] + t with."""
+        if sampling is None or not sampling.filtered:
+            return lambda logits, _out_len: self._sample(logits, temperature)
+        dev = self.device
+        base = sampling.seed if sampling.seed is not None \
+            else self.derive_seed()
+        n = batch * T
+        temps = torch.full((n,), float(sampling.temperature), device=dev)
+        ks = torch.full((n,), int(sampling.top_k or 0), dtype=torch.int32,
+                        device=dev)
+        ps = torch.full((n,), float(sampling.top_p), device=dev)
+        seeds = (int(base) + torch.arange(batch, dtype=torch.int64,
+                                          device=dev)).repeat_interleave(T)
+        offs = torch.arange(T, dtype=torch.int32, device=dev)
+
+        def sample(logits, out_len):
+            steps = (out_len.unsqueeze(1) + offs).reshape(-1)
+            return ops.sample_filtered(logits, temps, ks, ps, seeds, steps)
+
+        return sample
+
+    def _spec_done(self, st: dict, stop_on_eos: bool) -> bool:
+        """Host check (a sync): every row at its budget or past an EOS."""
+        out_len = st["out_len"]
+        done = out_len >= st["max_new"]
+        if stop_on_eos:
+            cols = torch.arange(st["out_buf"].shape[1], device=self.device)
+            done = done | ((st["out_buf"] == EOS_ID)
+                           & (cols[None, :] < out_len[:, None])).any(dim=1)
+        return bool(done.all())
+
+    def _spec_finish(self, st: dict, steps: int, B_req: int) -> None:
+        stats = st["stats"][:B_req].sum(dim=0).tolist()
+        self.last_spec = {"steps": steps, "drafted": int(stats[0]),
+                          "accepted": int(stats[1])}
 
     # ----- prefix-KV cache (shared prompt prefixes prefilled once) -----
     _PREFIX_MIN_TOKENS = 64
@@ -621,6 +775,7 @@ class GeneratorEngine:
         top_p: float = 1.0,
         seed: int | None = None,
         grammar=None,
+        speculative: int | None = None,
     ) -> list[str]:
         """Batched generation.  Returns decoded completions (prompt excluded).
 
@@ -638,6 +793,12 @@ class GeneratorEngine:
         the grammar even when the budget runs out.  ValueError, before any
         forward, when max_new_tokens is below the grammar's shortest
         completion.
+
+        speculative: prompt-lookup draft tokens per decode step (None: the
+        engine's spec_tokens; 0: off).  Exact: every emitted token is the
+        target model's own sample at its position.  Not available with a
+        grammar, the fp8 KV cache, TP or on_token: an explicit value > 0
+        then raises ValueError before any forward.
         """
         if not prompts:
             return []
@@ -647,6 +808,7 @@ class GeneratorEngine:
         handle = self.resolve_grammar(grammar)
         if handle is not None:
             self.check_grammar_budget(handle, max_new_tokens)
+        spec_k = self._resolve_spec(speculative, handle, on_token)
         import time as _time
 
         from sentio_amd.observability.kernel_timer import get_timer
@@ -657,7 +819,8 @@ class GeneratorEngine:
                 return self._generate_locked(
                     prompts, max_new_tokens, temperature, stop_on_eos,
                     on_token, _time,
-                    SamplingParams(temperature, top_k, top_p, seed, handle))
+                    SamplingParams(temperature, top_k, top_p, seed, handle),
+                    spec_k)
         finally:
             self._gen_lock.release()
 
@@ -676,7 +839,8 @@ class GeneratorEngine:
 
     def _generate_locked(self, prompts, max_new_tokens, temperature,
                          stop_on_eos, on_token, _time,
-                         sampling: SamplingParams | None = None) -> list[str]:
+                         sampling: SamplingParams | None = None,
+                         spec_k: int = 0) -> list[str]:
         B_req = len(prompts)
         if self.device != "cpu":
             pad = self._bucket_batch(B_req) - B_req
@@ -723,11 +887,35 @@ class GeneratorEngine:
         # (every 16 steps) or the streaming callback — not per token.
         toks_buf = torch.zeros(B, max_new_tokens, dtype=torch.int64,
                                device=self.device)
+        if max_new_tokens < 1:
+            spec_k = 0      # nothing to emit: the one-token path's empty loop
+        if spec_k > 0 and sampling is not None and sampling.filtered \
+                and sampling.seed is None:
+            # one base seed for the first token's sampler and the loop's
+            sampling = replace(sampling, seed=self.derive_seed())
         sampler = self._make_sampler(sampling, temperature, B,
                                      max_new_tokens)
         cur = sampler(logits, 0)
         n_steps = max_new_tokens
-        for step in range(max_new_tokens):
+        row_lens = None
+        if spec_k > 0:
+            # speculative loop: up to spec_k + 1 tokens per row and step;
+            # the host looks at the device state every 16 steps
+            pre = list(prefix_ids) if use_prefix else []
+            st = self._spec_state(
+                sess, [pre + padded[b][:lens[b]] for b in range(B)], cur,
+                max_new_tokens)
+            sample = self._spec_sampler(sampling, temperature, B, spec_k + 1)
+            n_steps = 0
+            for it in range(max_new_tokens - 1):
+                self._spec_step(sess, st, spec_k, sample)
+                n_steps = it + 1
+                if it % 16 == 15 and self._spec_done(st, stop_on_eos):
+                    break
+            toks_buf = st["out_buf"]
+            row_lens = st["out_len"][:B_req].cpu().tolist()
+            self._spec_finish(st, n_steps, B_req)
+        for step in range(0 if spec_k > 0 else max_new_tokens):
             toks_buf[:, step] = cur
             if on_token is not None:
                 on_token(step, cur.cpu().tolist()[:B_req])
@@ -750,10 +938,16 @@ class GeneratorEngine:
             metrics_collector.inc("rag_llm_tokens_total",
                                   float(n_prompt), kind="prompt")
             metrics_collector.inc("rag_llm_tokens_total",
-                                  float(B_req * n_steps), kind="completion")
+                                  float(sum(row_lens) if row_lens is not None
+                                        else B_req * n_steps),
+                                  kind="completion")
         except Exception:
             pass
-        rows = toks_buf[:B_req, :n_steps].cpu().tolist()
+        if row_lens is not None:
+            rows = [r[:n] for r, n in
+                    zip(toks_buf[:B_req].cpu().tolist(), row_lens)]
+        else:
+            rows = toks_buf[:B_req, :n_steps].cpu().tolist()
         out = []
         for row in rows:
             ids = []
@@ -822,7 +1016,8 @@ class GeneratorEngine:
     @torch.inference_mode()
     def stream(self, prompt: str, max_new_tokens: int = 128,
                temperature: float = 0.3, top_k: int = 0, top_p: float = 1.0,
-               seed: int | None = None, grammar=None) -> Iterator[str]:
+               seed: int | None = None, grammar=None,
+               speculative: int | None = None) -> Iterator[str]:
         """Yield text deltas token-by-token (single prompt) — the on-device
         equivalent of the reference's SSE streaming (openai.py:149-157).
         Holds the generation lock for the stream's duration (the pooled
@@ -830,26 +1025,56 @@ class GeneratorEngine:
         handle = self.resolve_grammar(grammar)
         if handle is not None:
             self.check_grammar_budget(handle, max_new_tokens)
+        spec_k = self._resolve_spec(speculative, handle)
         with self._gen_lock:
             yield from self._stream_locked(prompt, max_new_tokens, temperature,
-                                           top_k, top_p, seed, handle)
+                                           top_k, top_p, seed, handle, spec_k)
 
     def _stream_locked(self, prompt: str, max_new_tokens: int,
                        temperature: float, top_k: int = 0,
                        top_p: float = 1.0,
                        seed: int | None = None,
-                       grammar=None) -> Iterator[str]:
+                       grammar=None, spec_k: int = 0) -> Iterator[str]:
         prompt_budget = self.max_seq - max_new_tokens - 1
         ids = self.tokenizer.encode(prompt[-4 * prompt_budget:], prompt_budget)
         tokens = torch.tensor([ids], dtype=torch.int64, device=self.device)
         sess = self._decode_session(1, self.max_seq)
         logits = sess.prefill(tokens)
-        sampler = self._make_sampler(
-            SamplingParams(temperature, top_k, top_p, seed, grammar),
-            temperature, 1, max_new_tokens)
+        params = SamplingParams(temperature, top_k, top_p, seed, grammar)
+        if max_new_tokens < 1:
+            spec_k = 0      # nothing to emit: the one-token path's empty loop
+        if spec_k > 0 and params.filtered and seed is None:
+            # one base seed for the first token's sampler and the loop's
+            params = replace(params, seed=self.derive_seed())
+        sampler = self._make_sampler(params, temperature, 1, max_new_tokens)
         cur = sampler(logits, 0)
         generated: list[int] = []
         emitted = ""
+        if spec_k > 0:
+            # speculative stream: one verify step, then a delta for each
+            # token it emitted (the host reads the device state per step)
+            st = self._spec_state(sess, [ids], cur, max_new_tokens)
+            sample = self._spec_sampler(params, temperature, 1, spec_k + 1)
+            seen = steps = 0
+            while True:
+                n = int(st["out_len"][0])
+                new = st["out_buf"][0, seen:n].tolist()
+                seen = n
+                for t in new:
+                    if t == EOS_ID:
+                        break
+                    generated.append(t)
+                    text = self.tokenizer.decode(generated)
+                    if len(text) > len(emitted):
+                        delta = text[len(emitted):]
+                        emitted = text
+                        yield delta
+                if EOS_ID in new or n >= max_new_tokens:
+                    break
+                self._spec_step(sess, st, spec_k, sample)
+                steps += 1
+            self._spec_finish(st, steps, 1)
+            return
         for step in range(max_new_tokens):
             t = int(cur.item())
             if t == EOS_ID:

@@ -560,6 +560,69 @@ class Transformer:
             last_idx = suffix_lens.long() - 1
         return self.logits(hidden, last_idx)
 
+    def verify_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+        """Speculative-decoding verify forward: tokens [B, T], token t of
+        row b at position cache.seq_lens[b] + t, → logits [B*T, V] (row
+        b*T + t: the distribution of the token after t).  Writes the T new
+        K/V rows per layer and does NOT advance seq_lens: the caller adds
+        the number of tokens it accepts.  On the GPU every projection runs
+        through ops.lt_linear at M = B*T and attention through
+        ops.decode_attention_verify, with no host sync, so a session can
+        capture it per (batch, T).  On the CPU the T tokens run as T
+        one-token reference steps on a scratch seq_lens, so the logits equal
+        the plain path's by construction."""
+        if cache.fp8:
+            raise ValueError("verify_step has no fp8 KV-cache variant")
+        if self.tp.enabled:
+            raise ValueError("verify_step does not run tensor-parallel")
+        B, T = tokens.shape
+        if not tokens.is_cuda:
+            return self._verify_step_ref(tokens, cache)
+        M, d = B * T, self.cfg.dim
+        x = self.w.tok_emb[tokens.reshape(-1)].view(M, 1, d)
+        eps = self.cfg.norm_eps
+        layers = self.w.layers
+        n = len(layers)
+        normed = ops.rmsnorm(x, layers[0]["attn_norm"], eps)
+        for i, layer in enumerate(layers):
+            qkv = ops.lt_linear(normed.view(M, d), layer["wqkv"])
+            a = ops.decode_attention_verify(
+                qkv, cache.k[i], cache.v[i], self.rope_cos, self.rope_sin,
+                cache.seq_lens, T, self.scale)
+            a = ops.lt_linear(a, layer["wo"]).view(M, 1, d)
+            normed, x = ops.rmsnorm_residual(a, x, layer["ffn_norm"], eps)
+            gu = ops.lt_linear(normed.view(M, d), layer["w_gate_up"])
+            f = ops.lt_linear(ops.swiglu_packed(gu), layer["w_down"])
+            w_next = layers[i + 1]["attn_norm"] if i + 1 < n else self.w.final_norm
+            normed, x = ops.rmsnorm_residual(f.view(M, 1, d), x, w_next, eps)
+        return ops.lt_linear(normed.view(M, d), self.w.lm_head).float()
+
+    def _verify_step_ref(self, tokens: torch.Tensor,
+                         cache: KVCache) -> torch.Tensor:
+        """verify_step as T one-token steps.  A row whose token t sits at or
+        past the cache's end is left out of that step (zero logits), like
+        the kernel leaves it out."""
+        from types import SimpleNamespace
+
+        B, T = tokens.shape
+        out = torch.zeros(B, T, self.cfg.vocab_size, dtype=torch.float32,
+                          device=tokens.device)
+        for t in range(T):
+            pos = cache.seq_lens + t
+            live = (pos < cache.max_seq).nonzero().flatten()
+            if live.numel() == 0:
+                break
+            sub = SimpleNamespace(
+                k=[k[live] for k in cache.k], v=[v[live] for v in cache.v],
+                seq_lens=pos[live].contiguous(), fp8=False, scales=None,
+                max_seq=cache.max_seq)
+            out[live, t] = self.logits(
+                self.forward_decode(tokens[live, t:t + 1], sub))
+            for i in range(len(cache.k)):
+                cache.k[i][live] = sub.k[i]
+                cache.v[i][live] = sub.v[i]
+        return out.view(B * T, -1)
+
     def decode_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
         """tokens: [B, 1] the latest sampled token; returns logits [B, V]."""
         hidden = self.forward_decode(tokens, cache)

@@ -265,6 +265,51 @@ def decode_attention_fused(qkv, k_cache, v_cache, cos, sin, seq_lens,
                                             seq_lens, s)
 
 
+def decode_attention_verify(qkv, k_cache, v_cache, cos, sin, seq_lens, T: int,
+                            scale: float | None = None):
+    """ops.decode_attention_fused for T tokens per batch row in one launch
+    (the verify step of speculative decoding).  qkv: [B*T, (H+2*Hkv)*D] raw
+    projection, row b*T + t; seq_lens: [B] contiguous i32, the keys already
+    cached, i.e. the position of token t = 0 (only read).  Token t sits at
+    p = seq_lens[b] + t: q and k get RoPE at p, the k/v rows are written at
+    cache row p (bit-equal to decode_qkv_prep's), and query (b, t, h)
+    attends to rows [0, seq_lens[b]) plus the new rows 0..t.  A token with
+    p >= Smax writes nothing, is nobody's key and gets a zero output row.
+    D in {64, 128}, 2 <= T <= 8, (H/Hkv)*T <= 32; anything else raises
+    ValueError before a launch.  Returns [B*T, H*D]."""
+    if qkv.dim() != 2 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("qkv must be [B*T, (H+2*Hkv)*D], caches "
+                         "[B,Hkv,Smax,D]")
+    T = int(T)
+    if not 2 <= T <= 8:
+        raise ValueError(f"T must be in [2, 8], got {T}")
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    if D not in (64, 128):
+        raise ValueError(f"head dim must be 64 or 128, got {D}")
+    H = qkv.shape[1] // D - 2 * Hkv
+    if H <= 0 or H % Hkv or (H + 2 * Hkv) * D != qkv.shape[1]:
+        raise ValueError(
+            f"qkv width {qkv.shape[1]} is not (H+2*{Hkv})*{D} for a whole "
+            "number of query heads per kv head")
+    if (H // Hkv) * T > 32:
+        raise ValueError(f"query heads per kv head times T must be at most "
+                         f"32, got {H // Hkv} * {T}")
+    if qkv.shape[0] == 0 or qkv.shape[0] % T:
+        raise ValueError(f"qkv has {qkv.shape[0]} rows, not a multiple of "
+                         f"T={T}")
+    B = qkv.shape[0] // T
+    if seq_lens.dtype != torch.int32 or not seq_lens.is_contiguous() \
+            or seq_lens.numel() != B or k_cache.shape[0] < B:
+        raise ValueError("seq_lens must be a contiguous int32 [B] tensor and "
+                         "the caches hold at least B rows")
+    s = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    if _on_gpu(qkv):
+        return _require_hip().decode_attn_verify(
+            qkv.contiguous(), k_cache, v_cache, cos, sin, seq_lens, T, s)
+    return torch_ref.decode_attention_verify(qkv, k_cache, v_cache, cos, sin,
+                                             seq_lens, T, s)
+
+
 def _check_fp8_caches(k_cache, v_cache):
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
         raise ValueError("fp8 caches must be two [B,Hkv,Smax,D] tensors of "
@@ -614,6 +659,88 @@ def sample_slots(logits, slot, temperature, top_k, top_p, seed, step, active,
                            step, active, tok)
 
 
+def ngram_draft(hist, hist_len, room, K: int, n_max: int = 3):
+    """Prompt-lookup draft for speculative decoding.  hist int64 [B, L] holds
+    each row's tokens, hist_len int32 [B] of them valid, room int32 [B] caps
+    the draft.  For n = n_max .. 1, among the earlier occurrences of the
+    row's last n tokens that are followed by at least one token: the most
+    recent with K following tokens, else the most recent at all; the longest
+    n wins.  Returns (draft int64 [B, K], n_draft int32 [B]) with n_draft =
+    min(K, tokens after the match, room[b]), 0 without a match or with
+    room[b] <= 0; unused draft entries are 0."""
+    K, n_max = int(K), int(n_max)
+    if K < 1 or n_max < 1:
+        raise ValueError("K and n_max must be positive")
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 2 \
+            or hist.dtype != torch.int64 or hist.numel() == 0 \
+            or not hist.is_contiguous():
+        raise ValueError("hist must be a non-empty contiguous int64 [B, L] "
+                         "tensor")
+    B, dev = hist.shape[0], hist.device
+    _check_slot_array(hist_len, "hist_len", B, torch.int32, dev)
+    _check_slot_array(room, "room", B, torch.int32, dev)
+    if _on_gpu(hist):
+        draft, n_draft = _require_hip().ngram_draft(hist, hist_len, room, K,
+                                                    n_max)
+        return draft, n_draft
+    return torch_ref.ngram_draft(hist, hist_len, room, K, n_max)
+
+
+def spec_accept(sampled, draft, n_draft, out_buf, out_len, max_new: int, hist,
+                hist_len, seq_lens, cur, stats=None, room=None,
+                smax: int = 0):
+    """Accept step of speculative decoding, IN PLACE on out_buf int64
+    [B, >= max_new], out_len, hist int64 [B, L], hist_len, seq_lens (int32
+    [B]) and cur int64 [B].  sampled int64 [B, T]: the target's tokens at
+    the T verified positions; draft int64 [B, T-1], n_draft int32 [B].
+    a = leading i < n_draft[b] with sampled[b, i] == draft[b, i];
+    e = min(a + 1, max_new - out_len[b]), 0 for a row at its budget.
+    sampled[b, :e] is appended to out_buf and hist at the row's offsets,
+    out_len, hist_len and seq_lens advance by e and cur[b] becomes the last
+    emitted token (unchanged when e = 0).  stats int32 [B, 2] accumulates
+    (drafted, accepted) per row; one is made when not given.  room (int32
+    [B], optional) receives the next draft's clamp min(max_new - out_len -
+    1, smax - 1 - seq_lens).  Returns stats."""
+    if not isinstance(sampled, torch.Tensor) or sampled.dim() != 2 \
+            or sampled.shape[1] < 2 or sampled.dtype != torch.int64 \
+            or not sampled.is_contiguous():
+        raise ValueError("sampled must be a contiguous int64 [B, T >= 2] "
+                         "tensor")
+    B, T = sampled.shape
+    dev = sampled.device
+    if stats is None:
+        stats = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+    for t, name, dt, shape in (
+            (draft, "draft", torch.int64, (B, T - 1)),
+            (out_buf, "out_buf", torch.int64, (B, None)),
+            (hist, "hist", torch.int64, (B, None)),
+            (stats, "stats", torch.int32, (B, 2))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 \
+                or t.shape[0] != B or shape[1] not in (None, t.shape[1]) \
+                or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {dt} "
+                             f"[{B}, {shape[1] or 'n'}] tensor on {dev}")
+    for t, name in ((n_draft, "n_draft"), (out_len, "out_len"),
+                    (hist_len, "hist_len"), (seq_lens, "seq_lens")):
+        _check_slot_array(t, name, B, torch.int32, dev)
+    _check_slot_array(cur, "cur", B, torch.int64, dev)
+    if room is not None:
+        _check_slot_array(room, "room", B, torch.int32, dev)
+    max_new = int(max_new)
+    if not 0 <= max_new <= out_buf.shape[1]:
+        raise ValueError(f"max_new={max_new} exceeds out_buf's "
+                         f"{out_buf.shape[1]} columns")
+    if _on_gpu(sampled):
+        _require_hip().spec_accept(sampled, draft, n_draft, out_buf, out_len,
+                                   max_new, hist, hist_len, seq_lens, cur,
+                                   stats, room, int(smax))
+    else:
+        torch_ref.spec_accept(sampled, draft, n_draft, out_buf, out_len,
+                              max_new, hist, hist_len, seq_lens, cur, stats,
+                              room, int(smax))
+    return stats
+
+
 class GrammarTables:
     """The device tables of constrained sampling (see engines/grammar.py):
     next int16 [N, Vt], mask int32 [N, ceil(Vt/32)], dist int16 [N], plus
@@ -809,7 +936,7 @@ def gemm_bf16(a, b):
 
 
 __all__ = [
-    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
+    "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_verify", "ngram_draft", "spec_accept", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -272,6 +272,75 @@ torch::Tensor sample_filtered(torch::Tensor logits, torch::Tensor temperature,
   return out;
 }
 
+// ---- speculative decoding bookkeeping (sampling.hip).  Everything is read
+// or written in place at its kernel dtype: nothing is converted or copied.
+void check_spec(const torch::Tensor& t, const char* name,
+                torch::ScalarType dt, int64_t dim, int64_t rows) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous() &&
+              t.dim() == dim && t.size(0) == rows,
+              name, ": wrong dtype, shape or device");
+}
+
+std::vector<torch::Tensor> ngram_draft(torch::Tensor hist,
+                                       torch::Tensor hist_len,
+                                       torch::Tensor room, int64_t K,
+                                       int64_t n_max) {
+  TORCH_CHECK(hist.dim() == 2 && hist.numel() > 0, "hist must be [B, L]");
+  const long B = hist.size(0);
+  check_spec(hist, "hist", torch::kLong, 2, B);
+  check_spec(hist_len, "hist_len", torch::kInt, 1, B);
+  check_spec(room, "room", torch::kInt, 1, B);
+  TORCH_CHECK(K >= 1 && n_max >= 1, "K and n_max must be positive");
+  auto draft = torch::empty({B, K}, hist.options());
+  auto n_draft = torch::empty({B}, hist_len.options());
+  check_hip(sentio_ngram_draft((const long*)hist.data_ptr<int64_t>(),
+                               hist_len.data_ptr<int>(), room.data_ptr<int>(),
+                               (long*)draft.data_ptr<int64_t>(),
+                               n_draft.data_ptr<int>(), (int)B,
+                               (int)hist.size(1), (int)K, (int)n_max,
+                               stream()), "ngram_draft");
+  return {draft, n_draft};
+}
+
+void spec_accept(torch::Tensor sampled, torch::Tensor draft,
+                 torch::Tensor n_draft, torch::Tensor out_buf,
+                 torch::Tensor out_len, int64_t max_new, torch::Tensor hist,
+                 torch::Tensor hist_len, torch::Tensor seq_lens,
+                 torch::Tensor cur, torch::Tensor stats,
+                 c10::optional<torch::Tensor> room, int64_t smax) {
+  TORCH_CHECK(sampled.dim() == 2 && sampled.size(1) >= 2,
+              "sampled must be [B, T >= 2]");
+  const long B = sampled.size(0), T = sampled.size(1);
+  check_spec(sampled, "sampled", torch::kLong, 2, B);
+  check_spec(draft, "draft", torch::kLong, 2, B);
+  TORCH_CHECK(draft.size(1) == T - 1, "draft must be [B, T-1]");
+  check_spec(n_draft, "n_draft", torch::kInt, 1, B);
+  check_spec(out_buf, "out_buf", torch::kLong, 2, B);
+  check_spec(out_len, "out_len", torch::kInt, 1, B);
+  check_spec(hist, "hist", torch::kLong, 2, B);
+  check_spec(hist_len, "hist_len", torch::kInt, 1, B);
+  check_spec(seq_lens, "seq_lens", torch::kInt, 1, B);
+  check_spec(cur, "cur", torch::kLong, 1, B);
+  check_spec(stats, "stats", torch::kInt, 2, B);
+  TORCH_CHECK(stats.size(1) == 2, "stats must be [B, 2]");
+  TORCH_CHECK(max_new >= 0 && max_new <= out_buf.size(1),
+              "max_new exceeds out_buf's width");
+  int* room_p = nullptr;
+  if (room.has_value()) {
+    check_spec(*room, "room", torch::kInt, 1, B);
+    room_p = room->data_ptr<int>();
+  }
+  check_hip(sentio_spec_accept(
+                (const long*)sampled.data_ptr<int64_t>(),
+                (const long*)draft.data_ptr<int64_t>(),
+                n_draft.data_ptr<int>(), (long*)out_buf.data_ptr<int64_t>(),
+                out_len.data_ptr<int>(), (long*)hist.data_ptr<int64_t>(),
+                hist_len.data_ptr<int>(), seq_lens.data_ptr<int>(),
+                (long*)cur.data_ptr<int64_t>(), stats.data_ptr<int>(), room_p,
+                (int)B, (int)T, (int)out_buf.size(1), (int)hist.size(1),
+                (int)max_new, (int)smax, stream()), "spec_accept");
+}
+
 // In place on step and tok, so nothing here may convert or copy: every
 // tensor must already have its kernel dtype and be contiguous on the GPU.
 void sample_slots(torch::Tensor logits, c10::optional<torch::Tensor> slot,
@@ -597,6 +666,51 @@ torch::Tensor decode_attn_fused(torch::Tensor qkv, torch::Tensor kc,
   return out;
 }
 
+// Speculative-decoding verify attention: decode_attn_fused for T tokens per
+// batch row at positions seq_lens[b] + t, K/V streamed once per (b, kv
+// head) for all of them.  Writes the T new k/v rows; seq_lens is only read.
+// The split / wave plan is decode_attn_plan's.
+torch::Tensor decode_attn_verify(torch::Tensor qkv, torch::Tensor kc,
+                                 torch::Tensor vc, torch::Tensor cosT,
+                                 torch::Tensor sinT, torch::Tensor seq_lens,
+                                 int64_t T, double scale) {
+  check_bf16_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B*T, (H+2*Hkv)*D]");
+  check_caches(kc, vc);
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == torch::kInt &&
+              seq_lens.is_contiguous(),
+              "seq_lens must be a contiguous i32 GPU tensor");
+  TORCH_CHECK(T >= 2 && T <= 8, "T must be in [2, 8], got ", T);
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) % T == 0,
+              "qkv rows must be a multiple of T");
+  const int B = qkv.size(0) / T;
+  const int Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
+  const int H = (int)(qkv.size(1) / D) - 2 * Hkv;
+  TORCH_CHECK(H > 0 && H % Hkv == 0 &&
+              (long)(H + 2 * Hkv) * D == qkv.size(1), "qkv width mismatch");
+  TORCH_CHECK((H / Hkv) * T <= 32, "query heads per kv head times T must be "
+              "at most 32, got ", (H / Hkv) * T);
+  TORCH_CHECK(kc.size(0) >= B && seq_lens.numel() == B,
+              "batch mismatch between qkv, caches and seq_lens");
+  for (const auto* t : {&cosT, &sinT}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                t->is_contiguous() && t->dim() == 2 && t->size(0) >= Smax &&
+                t->size(1) == D / 2,
+                "rope tables must be contiguous f32 [>=Smax, D/2] on GPU");
+  }
+  auto out = torch::empty({B * T, (long)H * D}, qkv.options());
+  const auto [splits, waves] = decode_attn_plan(B, Hkv, Smax);
+  DecodeWorkspace ws(qkv, splits, B * T, Hkv, H / Hkv, D);
+  check_hip(sentio_decode_attn_verify(
+                qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                cosT.data_ptr<float>(), sinT.data_ptr<float>(),
+                seq_lens.data_ptr<int>(), ws.o_ptr, ws.ml_ptr, splits, waves,
+                B, (int)T, H, Hkv, Smax, D, (float)scale, stream()),
+            "decode_attn_verify");
+  return out;
+}
+
 // ---- FP8 (e4m3fn) KV cache: uint8 caches + fp32 [Hkv] scales
 void check_caches_u8(const torch::Tensor& kc, const torch::Tensor& vc) {
   for (const auto* t : {&kc, &vc}) {
@@ -878,6 +992,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_support", &sample_support);
   m.def("sample_filtered", &sample_filtered);
   m.def("sample_slots", &sample_slots);
+  m.def("ngram_draft", &ngram_draft);
+  m.def("spec_accept", &spec_accept);
   m.def("sample_constrained", &sample_constrained);
   m.def("sample_slots_constrained", &sample_slots_constrained);
   m.def("cosine_scores", &cosine_scores);
@@ -887,6 +1003,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn", &decode_attn);
   m.def("decode_attn_fused", &decode_attn_fused);
   m.def("decode_attn_fused_fp8", &decode_attn_fused_fp8);
+  m.def("decode_attn_verify", &decode_attn_verify);
   m.def("kv_store_fp8", &kv_store_fp8);
   m.def("decode_attn_plan", &decode_attn_plan);
   m.def("decode_gemm_plan", &decode_gemm_plan);

@@ -580,7 +580,123 @@ __global__ __launch_bounds__(SF_THREADS) void sample_constrained_kernel(
   }
 }
 
+// ------------------------------------------------- speculative bookkeeping
+// Prompt-lookup drafting and the accept step of speculative decoding, on the
+// device so the verify loop has no per-step host sync.  Integer work only.
+
+// One block per row.  hist [B, L] holds the row's tokens, hist_len[b] of
+// them valid.  For n = n_max .. 1: among the occurrences of the row's last
+// n tokens that start at i <= len - n - 1 (at least one token follows), the
+// most recent with K following tokens, else the most recent at all; the
+// longest n with any occurrence wins.  n_draft = min(K, tokens after the
+// match, room[b]), 0 without a match or with room[b] <= 0; draft entries
+// past n_draft are 0.
+#define NG_THREADS 256
+__global__ __launch_bounds__(NG_THREADS) void ngram_draft_kernel(
+    const long* __restrict__ hist, const int* __restrict__ hist_len,
+    const int* __restrict__ room, long* __restrict__ draft,
+    int* __restrict__ n_draft, int L, int K, int n_max) {
+  __shared__ int best[2];                  // [0]: with K followers, [1]: any
+  const int b = blockIdx.x;
+  const long* h = hist + (long)b * L;
+  const int len = max(0, min(hist_len[b], L));
+  const int rm = room[b];
+  int start = -1;                          // first follower of the match
+  if (rm > 0) {
+    for (int n = min(n_max, len - 1); n >= 1 && start < 0; --n) {
+      if (threadIdx.x < 2) best[threadIdx.x] = -1;
+      __syncthreads();
+      int full = -1, any = -1;
+      for (int i = threadIdx.x; i <= len - n - 1; i += NG_THREADS) {
+        bool eq = true;
+        for (int j = 0; j < n; ++j) eq = eq && h[i + j] == h[len - n + j];
+        if (eq) {
+          any = i;                         // i grows: the last hit stays
+          if (i + n + K <= len) full = i;
+        }
+      }
+      if (full >= 0) atomicMax(&best[0], full);
+      if (any >= 0) atomicMax(&best[1], any);
+      __syncthreads();
+      const int hit = best[0] >= 0 ? best[0] : best[1];
+      if (hit >= 0) start = hit + n;
+      __syncthreads();                     // best is reset next round
+    }
+  }
+  const int nd = start < 0 ? 0 : min(min(K, len - start), rm);
+  for (int j = threadIdx.x; j < K; j += NG_THREADS)
+    draft[(long)b * K + j] = j < nd ? h[start + j] : 0;
+  if (threadIdx.x == 0) n_draft[b] = nd;
+}
+
+// One thread per row.  sampled [B, T] are the target's tokens at the T
+// verified positions, draft [B, T-1] what was fed at positions 1 .. T-1.
+// a = leading i < n_draft[b] with sampled[b, i] == draft[b, i];
+// e = min(a + 1, max_new - out_len[b]) tokens are emitted (0 at the
+// budget): appended to out_buf [B, OW] and hist [B, L] at the row's own
+// offsets, out_len / hist_len / seq_lens advance by e, cur[b] becomes the
+// last emitted token.  stats [B, 2] accumulates (drafted, accepted) of rows
+// that emitted.  room (optional) receives the next step's draft clamp
+// min(max_new - out_len - 1, smax - 1 - seq_lens).
+__global__ void spec_accept_kernel(
+    const long* __restrict__ sampled, const long* __restrict__ draft,
+    const int* __restrict__ n_draft, long* __restrict__ out_buf,
+    int* __restrict__ out_len, long* __restrict__ hist,
+    int* __restrict__ hist_len, int* __restrict__ seq_lens,
+    long* __restrict__ cur, int* __restrict__ stats, int* __restrict__ room,
+    int B, int T, int OW, int L, int max_new, int smax) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long* s = sampled + (long)b * T;
+  const long* d = draft + (long)b * (T - 1);
+  const int nd = max(0, min(n_draft[b], T - 1));
+  int a = 0;
+  while (a < nd && s[a] == d[a]) ++a;
+  int ol = out_len[b], hl = hist_len[b];
+  const int e = max(0, min(a + 1, min(max_new, OW) - ol));
+  for (int i = 0; i < e; ++i) {
+    out_buf[(long)b * OW + ol + i] = s[i];
+    if (hl + i < L) hist[(long)b * L + hl + i] = s[i];
+  }
+  if (e > 0) {
+    cur[b] = s[e - 1];
+    out_len[b] = ol += e;
+    hist_len[b] = min(hl + e, L);
+    seq_lens[b] += e;
+    stats[b * 2 + 0] += nd;
+    stats[b * 2 + 1] += min(a, e);
+  }
+  if (room) room[b] = min(max_new - ol - 1, smax - 1 - seq_lens[b]);
+}
+
 extern "C" {
+
+hipError_t sentio_ngram_draft(const long* hist, const int* hist_len,
+                              const int* room, long* draft, int* n_draft,
+                              int B, int L, int K, int n_max,
+                              hipStream_t stream) {
+  if (B <= 0 || L <= 0 || K < 1 || n_max < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ngram_draft_kernel, dim3(B), dim3(NG_THREADS), 0, stream,
+                     hist, hist_len, room, draft, n_draft, L, K, n_max);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_spec_accept(const long* sampled, const long* draft,
+                              const int* n_draft, long* out_buf, int* out_len,
+                              long* hist, int* hist_len, int* seq_lens,
+                              long* cur, int* stats, int* room, int B, int T,
+                              int OW, int L, int max_new, int smax,
+                              hipStream_t stream) {
+  if (B <= 0 || T < 2 || OW <= 0 || L <= 0 || max_new < 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(spec_accept_kernel, dim3((B + 63) / 64), dim3(64), 0,
+                     stream, sampled, draft, n_draft, out_buf, out_len, hist,
+                     hist_len, seq_lens, cur, stats, room, B, T, OW, L,
+                     max_new, smax);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 static bool sc_tables_ok(int V, int Vt, int N, int W, int max_dist) {
   return V > 0 && Vt > 0 && N >= 1 && N <= 32767 && W == (Vt + 31) / 32 &&

@@ -99,6 +99,22 @@ hipError_t sentio_sample_slots_constrained(
     const unsigned char* active, long* tok, int* state, int* left,
     const short* next, const int* mask, const short* dist, long R, int S,
     int V, int Vt, int N, int W, int max_dist, hipStream_t stream);
+// prompt-lookup draft: hist int64 [B, L], hist_len / room int32 [B] ->
+// draft int64 [B, K], n_draft int32 [B]; dims are (B, L, K, n_max)
+hipError_t sentio_ngram_draft(const long* hist, const int* hist_len,
+                              const int* room, long* draft, int* n_draft,
+                              int B, int L, int K, int n_max,
+                              hipStream_t stream);
+// speculative accept, in place on out_buf [B, OW], out_len, hist [B, L],
+// hist_len, seq_lens, cur and stats int32 [B, 2]; sampled int64 [B, T],
+// draft int64 [B, T-1]; room int32 [B] or null; dims are (B, T, OW, L,
+// max_new, smax)
+hipError_t sentio_spec_accept(const long* sampled, const long* draft,
+                              const int* n_draft, long* out_buf, int* out_len,
+                              long* hist, int* hist_len, int* seq_lens,
+                              long* cur, int* stats, int* room, int B, int T,
+                              int OW, int L, int max_new, int smax,
+                              hipStream_t stream);
 
 // ---- retrieval.hip
 // index matrix first, queries second; dims are (N, D, B)
@@ -157,6 +173,17 @@ hipError_t sentio_decode_attn_fused_fp8(
     const float* v_scale, const float* k_inv, const float* v_inv, float* ws_o,
     float* ws_ml, int splits, int waves, int B, int H, int Hkv, int Smax,
     int D, float scale, hipStream_t stream);
+// as sentio_decode_attn_fused for T tokens per batch row (2 <= T <= 8,
+// (H/Hkv)*T <= 32): qkv is [B*T, (H+2*Hkv)*D], row b*T + t sits at position
+// seq_lens[b] + t; out is [B*T, H*D]; T sits between B and H.  With
+// splits > 1 the workspaces hold B*T "batch rows" of partials
+hipError_t sentio_decode_attn_verify(const void* qkv, void* kc, void* vc,
+                                     void* out, const float* cosT,
+                                     const float* sinT, const int* seq_lens,
+                                     float* ws_o, float* ws_ml, int splits,
+                                     int waves, int B, int T, int H, int Hkv,
+                                     int Smax, int D, float scale,
+                                     hipStream_t stream);
 // bf16 sources [n, Hkv, S_src, D] -> uint8 caches [B, Hkv, Smax, D] at
 // rows[i], first S rows; reciprocals only; dims are (n, B, Hkv, S_src, S,
 // Smax, D) — S_src and S sit BEFORE Smax

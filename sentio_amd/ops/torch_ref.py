@@ -477,6 +477,87 @@ def decode_attention_fused(
     return decode_attention(q, k_cache, v_cache, seq_lens + 1, scale)
 
 
+def decode_attention_verify(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    cos: torch.Tensor, sin: torch.Tensor, seq_lens: torch.Tensor, T: int,
+    scale: float | None = None,
+) -> torch.Tensor:
+    """Reference of ops.decode_attention_verify: token t of row b (qkv row
+    b*T + t) is one decode_attention_fused step at position seq_lens[b] + t,
+    the T steps in order, so token t sees the cache rows below seq_lens[b]
+    and the new rows 0..t.  A token at or past Smax is skipped: no write,
+    zero output.  seq_lens is not changed.  Returns [B*T, H*D]."""
+    B = qkv.shape[0] // T
+    Hkv, smax, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
+    H = qkv.shape[1] // D - 2 * Hkv
+    out = torch.zeros(B, T, H * D, dtype=qkv.dtype, device=qkv.device)
+    rows = qkv.view(B, T, -1)
+    for t in range(T):
+        pos = seq_lens + t
+        live = ((pos >= 0) & (pos < smax)).nonzero().flatten()
+        if live.numel() == 0:
+            continue
+        # the cache rows of the live batch rows, gathered and put back
+        kc, vc = k_cache[live], v_cache[live]
+        o = decode_attention_fused(rows[live, t].contiguous(), kc, vc, cos,
+                                   sin, pos[live].contiguous(), scale)
+        k_cache[live], v_cache[live] = kc, vc
+        out[live, t] = o.reshape(live.numel(), H * D)
+    return out.view(B * T, H * D)
+
+
+def ngram_draft(hist: torch.Tensor, hist_len: torch.Tensor,
+                room: torch.Tensor, K: int, n_max: int = 3):
+    """Reference of ops.ngram_draft (see there)."""
+    B, L = hist.shape
+    draft = torch.zeros(B, K, dtype=torch.int64)
+    n_draft = torch.zeros(B, dtype=torch.int32)
+    for b in range(B):
+        n_len = max(0, min(int(hist_len[b]), L))
+        h = hist[b, :n_len].tolist()
+        if int(room[b]) <= 0:
+            continue
+        for n in range(min(n_max, n_len - 1), 0, -1):
+            hits = [i for i in range(n_len - n) if h[i:i + n] == h[n_len - n:]]
+            if not hits:
+                continue
+            full = [i for i in hits if i + n + K <= n_len]
+            start = (full[-1] if full else hits[-1]) + n
+            nd = min(K, n_len - start, int(room[b]))
+            draft[b, :nd] = torch.tensor(h[start:start + nd],
+                                         dtype=torch.int64)
+            n_draft[b] = nd
+            break
+    return draft.to(hist.device), n_draft.to(hist.device)
+
+
+def spec_accept(sampled, draft, n_draft, out_buf, out_len, max_new, hist,
+                hist_len, seq_lens, cur, stats, room=None, smax: int = 0):
+    """Reference of ops.spec_accept (see there), in place."""
+    B, T = sampled.shape
+    L = hist.shape[1]
+    for b in range(B):
+        nd = max(0, min(int(n_draft[b]), T - 1))
+        a = 0
+        while a < nd and int(sampled[b, a]) == int(draft[b, a]):
+            a += 1
+        ol, hl = int(out_len[b]), int(hist_len[b])
+        e = max(0, min(a + 1, min(max_new, out_buf.shape[1]) - ol))
+        if e > 0:
+            out_buf[b, ol:ol + e] = sampled[b, :e]
+            w = max(0, min(e, L - hl))
+            hist[b, hl:hl + w] = sampled[b, :w]
+            cur[b] = sampled[b, e - 1]
+            out_len[b] = ol + e
+            hist_len[b] = min(hl + e, L)
+            seq_lens[b] += e
+            stats[b, 0] += nd
+            stats[b, 1] += min(a, e)
+        if room is not None:
+            room[b] = min(max_new - int(out_len[b]) - 1,
+                          smax - 1 - int(seq_lens[b]))
+
+
 # ---- FP8 (e4m3fn) KV cache: uint8 storage, static fp32 scales per kv head
 FP8_E4M3_MAX = 448.0
 
