@@ -201,9 +201,59 @@ def _attn_scale(q, scale: float | None) -> float:
     return float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
 
 
+_FLASH_HEAD_DIMS = (32, 64, 96, 128)
+
+
+def _check_attn_q(q) -> None:
+    if not isinstance(q, torch.Tensor) or q.dim() != 4 or q.numel() == 0:
+        raise ValueError("q must be a non-empty [B, S, H, D] tensor")
+
+
+def _check_kv_lens(kv_lens, q) -> None:
+    """Shape, dtype and device only: the values stay on the device."""
+    if not isinstance(kv_lens, torch.Tensor) or kv_lens.dim() != 1 \
+            or kv_lens.numel() != q.shape[0] \
+            or kv_lens.dtype not in (torch.int32, torch.int64) \
+            or kv_lens.device != q.device:
+        raise ValueError(f"kv_lens must be an int32 or int64 [{q.shape[0]}] "
+                         f"tensor on {q.device}")
+
+
+def _check_flash_gpu(q, *rest) -> None:
+    """What the prefill kernel is instantiated for."""
+    if any(t.dtype != torch.bfloat16 for t in (q, *rest)):
+        raise ValueError("attention inputs must be bf16 on the GPU, got "
+                         + " / ".join(str(t.dtype) for t in (q, *rest)))
+    if q.shape[3] not in _FLASH_HEAD_DIMS:
+        raise ValueError(f"head dim must be one of {_FLASH_HEAD_DIMS} on the "
+                         f"GPU, got {q.shape[3]}")
+
+
 def attention(q, k, v, causal: bool = True, scale: float | None = None,
               kv_lens=None):
+    """Prefill attention with GQA: q [B, S, H, D], k and v [B, S, Hkv, D]
+    with Hkv dividing H; kv_lens: optional integer [B] on q's device, keys at
+    or past kv_lens[b] are ignored (a row with no allowed key gives zeros).
+    On the GPU: bf16, D in {32, 64, 96, 128}.  Anything else raises
+    ValueError before a launch.  Returns [B, S, H, D]."""
+    _check_attn_q(q)
+    B, S, H, D = q.shape
+    for name, t in (("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 \
+                or t.device != q.device:
+            raise ValueError(f"{name} must be a [B, S, Hkv, D] tensor on "
+                             f"{q.device}")
+    if v.shape != k.shape or k.shape[0] != B or k.shape[1] != S \
+            or k.shape[3] != D or k.shape[2] < 1:
+        raise ValueError(f"k and v must both be [{B}, {S}, Hkv, {D}], got "
+                         f"{tuple(k.shape)} / {tuple(v.shape)}")
+    if H % k.shape[2]:
+        raise ValueError(f"{k.shape[2]} kv heads do not divide {H} query "
+                         "heads")
+    if kv_lens is not None:
+        _check_kv_lens(kv_lens, q)
     if _on_gpu(q):
+        _check_flash_gpu(q, k, v)
         if kv_lens is None:
             kv_lens = torch.full((q.shape[0],), q.shape[1], dtype=torch.int32,
                                  device=q.device)
@@ -219,9 +269,34 @@ def attention_cache(q, k_cache, v_cache, kv_lens, q_off: int,
     """Causal prefill attention for a SUFFIX of queries against the KV
     cache (prefix-KV caching): q [B, S_suf, H, D] at absolute positions
     q_off..q_off+S_suf-1; caches [B, Hkv, Smax, D]; kv_lens [B] absolute
-    valid lengths (prefix + suffix)."""
+    valid lengths (prefix + suffix), an integer tensor on q's device.  The
+    caches are contiguous, of q's dtype and on q's device, may hold more
+    batch rows than q, and Hkv divides H; q_off >= 0.  On the GPU: bf16, D
+    in {32, 64, 96, 128}.  Anything else raises ValueError before a
+    launch."""
+    _check_attn_q(q)
+    B, S, H, D = q.shape
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 \
+                or t.dtype != q.dtype or not t.is_contiguous() \
+                or t.device != q.device:
+            raise ValueError(f"{name} must be a contiguous {q.dtype} "
+                             f"[Bc, Hkv, Smax, D] tensor on {q.device}")
+    if v_cache.shape != k_cache.shape or k_cache.shape[3] != D \
+            or k_cache.shape[1] < 1 or k_cache.shape[2] < 1:
+        raise ValueError(f"caches must both be [Bc, Hkv, Smax, {D}], got "
+                         f"{tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if k_cache.shape[0] < B:
+        raise ValueError(f"cache has {k_cache.shape[0]} batch rows for {B}")
+    if H % k_cache.shape[1]:
+        raise ValueError(f"{k_cache.shape[1]} kv heads do not divide {H} "
+                         "query heads")
+    _check_kv_lens(kv_lens, q)
+    if int(q_off) < 0:
+        raise ValueError(f"q_off must be >= 0, got {q_off}")
     s = _attn_scale(q, scale)
     if _on_gpu(q):
+        _check_flash_gpu(q)
         return _require_hip().flash_attn_cache(
             q.contiguous(), k_cache, v_cache,
             kv_lens.to(torch.int32).contiguous(), s, int(q_off))

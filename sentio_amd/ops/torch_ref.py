@@ -119,7 +119,11 @@ def attention(
             < kv_lens.view(B, 1, 1, 1)
         )
         scores = scores.masked_fill(~key_valid, float("-inf"))
-    probs = torch.softmax(scores, dim=-1)
+    # a query row with no allowed key (kv_lens[b] == 0) gives zeros, as the
+    # kernel does, not softmax's NaN
+    no_key = torch.isneginf(scores).all(dim=-1, keepdim=True)
+    probs = torch.softmax(scores.masked_fill(no_key, 0.0), dim=-1)
+    probs = probs.masked_fill(no_key, 0.0)
     out = probs @ vf  # [B,H,S,D]
     return out.permute(0, 2, 1, 3).contiguous().to(q.dtype)
 
@@ -637,7 +641,10 @@ def attention_cache(
 ) -> torch.Tensor:
     """Suffix-against-cache causal attention (prefix-KV-cached prefill).
     q: [B, S_suf, H, D] at absolute positions q_off + i;
-    k_cache/v_cache: [B, Hkv, Smax, D]; kv_lens: [B] absolute lengths."""
+    k_cache/v_cache: [B, Hkv, Smax, D]; kv_lens: [B] absolute lengths.
+    Key 0 is within every query's horizon, so only kv_lens[b] == 0 leaves a
+    row without keys: the empty softmax times the empty V gives zeros, as
+    the kernel does."""
     B, S, H, D = q.shape
     Hkv = k_cache.shape[1]
     rep = H // Hkv
