@@ -11,6 +11,11 @@ dot product; search streams the index through a hipBLASLt TN GEMM
 
 The doc payloads (text + metadata) stay on host — only vectors and the
 id-mapping live in HBM.  Multi-GPU sharding wraps this class (parallel/shard).
+
+dtype="fp8" (opt-in) stores e4m3fn codes with one fp32 scale per row instead
+(dim + 4 bytes per document against 2 * dim; torch_ref.index_quantize is the
+spec) and searches with ops.cosine_topk_fp8, a fused scan + top-k kernel
+that writes no [B, N] score matrix.
 """
 
 from __future__ import annotations
@@ -30,13 +35,28 @@ class DenseIndex:
         self,
         dim: int = 1024,
         device: str = "cpu",
-        dtype: torch.dtype = torch.float16,
+        dtype: torch.dtype | str = torch.float16,
     ) -> None:
         self.dim = dim
         self.device = device
-        # fp16 halves scan bytes vs fp32; fp32 used on CPU for exactness
-        self.dtype = dtype if device != "cpu" else torch.float32
-        self._vecs = torch.empty(0, dim, dtype=self.dtype, device=device)
+        self.fp8 = dtype in ("fp8", torch.float8_e4m3fn)
+        if isinstance(dtype, str) and not self.fp8:
+            raise ValueError(f"unknown index dtype {dtype!r}")
+        if self.fp8:
+            from sentio_amd import ops
+
+            if not ops.fp8_index_dim_ok(dim):
+                raise ValueError("the fp8 index serves dim % 32 == 0 and "
+                                 f"dim <= 1024, got {dim}")
+            # codes on the CPU too; _vecs stays empty
+            self.dtype = torch.float8_e4m3fn
+            self._vecs = torch.empty(0, dim, dtype=torch.float16, device=device)
+        else:
+            # fp16 halves scan bytes vs fp32; fp32 used on CPU for exactness
+            self.dtype = dtype if device != "cpu" else torch.float32
+            self._vecs = torch.empty(0, dim, dtype=self.dtype, device=device)
+        self._codes = torch.empty(0, dim, dtype=torch.uint8, device=device)
+        self._scales = torch.empty(0, dtype=torch.float32, device=device)
         self._size = 0
         self.doc_ids: list[str] = []
         self._docs: dict[str, Document] = {}
@@ -48,10 +68,20 @@ class DenseIndex:
     # ----- build -----
     def _ensure_capacity(self, extra: int) -> None:
         need = self._size + extra
-        cap = self._vecs.shape[0]
+        cap = self._codes.shape[0] if self.fp8 else self._vecs.shape[0]
         if need <= cap:
             return
         new_cap = max(need, cap + self.GROW, int(cap * 1.5))
+        if self.fp8:
+            codes = torch.empty(new_cap, self.dim, dtype=torch.uint8,
+                                device=self.device)
+            scales = torch.empty(new_cap, dtype=torch.float32,
+                                 device=self.device)
+            if self._size:
+                codes[: self._size] = self._codes[: self._size]
+                scales[: self._size] = self._scales[: self._size]
+            self._codes, self._scales = codes, scales
+            return
         new = torch.empty(new_cap, self.dim, dtype=self.dtype, device=self.device)
         if self._size:
             new[: self._size] = self._vecs[: self._size]
@@ -68,7 +98,14 @@ class DenseIndex:
             self._ensure_capacity(n)
             emb = embeddings.to(self.device, torch.float32)
             emb = emb / emb.norm(dim=1, keepdim=True).clamp_min(1e-12)
-            self._vecs[self._size : self._size + n] = emb.to(self.dtype)
+            if self.fp8:
+                from sentio_amd.ops import torch_ref
+
+                codes, scales = torch_ref.index_quantize(emb)
+                self._codes[self._size : self._size + n] = codes
+                self._scales[self._size : self._size + n] = scales
+            else:
+                self._vecs[self._size : self._size + n] = emb.to(self.dtype)
             self._size += n
             for d in docs:
                 self.doc_ids.append(d.id)
@@ -100,7 +137,9 @@ class DenseIndex:
         q = query.to(self.device, torch.float32)
         q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
 
-        if self.device != "cpu":
+        if self.fp8:
+            vals, idx = self._topk_fp8(q, k)
+        elif self.device != "cpu":
             from sentio_amd import ops
 
             vals, idx = ops.cosine_topk(q.to(self.dtype), self._vecs[: self._size], k)
@@ -138,7 +177,9 @@ class DenseIndex:
         k = min(top_k, self._size)
         q = query.to(self.device, torch.float32)
         q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
-        if self.device != "cpu":
+        if self.fp8:
+            vals, idx = self._topk_fp8(q, k)
+        elif self.device != "cpu":
             from sentio_amd import ops
 
             vals, idx = ops.cosine_topk(q.to(self.dtype),
@@ -156,6 +197,18 @@ class DenseIndex:
                                              device=idx.device)], 1)
         return vals, idx
 
+    def _topk_fp8(self, q: torch.Tensor, k: int
+                  ) -> tuple[torch.Tensor, torch.Tensor]:
+        """k <= size best rows of the fp8 index for normalised fp32 queries
+        (fp16 into the kernel, as on the fp16 path).  The kernel selects at
+        most 128 per query: a larger k (top_k, or a filtered search's
+        top_k * 4) raises ValueError."""
+        from sentio_amd import ops
+
+        return ops.cosine_topk_fp8(q.to(torch.float16),
+                                   self._codes[: self._size],
+                                   self._scales[: self._size], k)
+
     def get_document(self, doc_id: str) -> Document | None:
         return self._docs.get(doc_id)
 
@@ -166,7 +219,12 @@ class DenseIndex:
 
     def clear(self) -> None:
         with self._lock:
-            self._vecs = torch.empty(0, self.dim, dtype=self.dtype, device=self.device)
+            self._vecs = torch.empty(0, self.dim, dtype=self._vecs.dtype,
+                                     device=self.device)
+            self._codes = torch.empty(0, self.dim, dtype=torch.uint8,
+                                      device=self.device)
+            self._scales = torch.empty(0, dtype=torch.float32,
+                                       device=self.device)
             self._size = 0
             self.doc_ids.clear()
             self._docs.clear()
@@ -175,21 +233,36 @@ class DenseIndex:
     # here the index itself persists: HBM→disk) -----
     def save(self, path: str) -> None:
         with self._lock:
-            torch.save(
-                {
-                    "dim": self.dim,
-                    "vecs": self._vecs[: self._size].to("cpu"),
-                    "doc_ids": self.doc_ids,
-                    "docs": [self._docs[d].to_dict() for d in self.doc_ids],
-                },
-                path,
-            )
+            state = {
+                "dim": self.dim,
+                "doc_ids": self.doc_ids,
+                "docs": [self._docs[d].to_dict() for d in self.doc_ids],
+            }
+            if self.fp8:
+                state["dtype"] = "fp8"
+                state["codes"] = self._codes[: self._size].to("cpu")
+                state["scales"] = self._scales[: self._size].to("cpu")
+            else:
+                state["vecs"] = self._vecs[: self._size].to("cpu")
+            torch.save(state, path)
 
     @classmethod
     def load(cls, path: str, device: str = "cpu") -> "DenseIndex":
         state = torch.load(path, map_location="cpu", weights_only=False)
-        idx = cls(dim=state["dim"], device=device)
         docs = [Document.from_dict(d) for d in state["docs"]]
+        if state.get("dtype") == "fp8":
+            # codes and scales byte for byte: no re-quantisation
+            idx = cls(dim=state["dim"], device=device, dtype="fp8")
+            n = len(docs)
+            idx._ensure_capacity(n)
+            idx._codes[:n] = state["codes"].to(device)
+            idx._scales[:n] = state["scales"].to(device)
+            idx._size = n
+            for d in docs:
+                idx.doc_ids.append(d.id)
+                idx._docs[d.id] = d
+            return idx
+        idx = cls(dim=state["dim"], device=device)
         vecs = state["vecs"].to(torch.float32)
         if len(docs):
             idx.add(docs, vecs)
@@ -201,6 +274,8 @@ class DenseIndex:
             "size": self._size,
             "dim": self.dim,
             "device": str(self.device),
-            "dtype": str(self.dtype),
-            "hbm_bytes": self._vecs.element_size() * self._vecs.nelement(),
+            "dtype": "fp8" if self.fp8 else str(self.dtype),
+            "hbm_bytes": (self._codes.nelement() + 4 * self._scales.nelement()
+                          if self.fp8 else
+                          self._vecs.element_size() * self._vecs.nelement()),
         }

@@ -542,6 +542,54 @@ def cosine_topk(q, mat, k: int):
     return torch_ref.cosine_topk(q, mat, k)
 
 
+_FP8_INDEX_KMAX = 128
+
+
+def fp8_index_dim_ok(dim: int) -> bool:
+    """Row widths the fp8 index scan serves."""
+    return 32 <= dim <= 1024 and dim % 32 == 0
+
+
+def cosine_topk_fp8(q, codes, scales, k: int):
+    """Fused scan + top-k over the fp8 (e4m3fn) dense index, no [B, N] score
+    matrix: q fp16 [B, D], codes uint8 [N, D], scales fp32 [N] (a row's
+    value is code * scale; torch_ref.index_quantize is the spec), 1 <= k <=
+    128, D % 32 == 0 and D <= 1024, any B.  Returns (scores f32 [B, k], rows
+    i64 [B, k]) by score descending, ties to the lower row, padded with
+    (-inf, -1) when k > N (torch_ref.cosine_topk_fp8 is the spec).  No host
+    sync.  Nothing is converted or copied: non-contiguous inputs, other
+    dtypes, mixed devices, k or D out of range raise ValueError before a
+    launch."""
+    for name, t, dt, nd in (("q", q, torch.float16, 2),
+                            ("codes", codes, torch.uint8, 2),
+                            ("scales", scales, torch.float32, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd \
+                or t.numel() == 0 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a non-empty contiguous {dt} "
+                             f"{nd}-d tensor")
+    if codes.device != q.device or scales.device != q.device:
+        raise ValueError("q, codes and scales must share a device")
+    if codes.shape[1] != q.shape[1] or scales.shape[0] != codes.shape[0]:
+        raise ValueError(f"q {tuple(q.shape)}, codes {tuple(codes.shape)} and "
+                         f"scales {tuple(scales.shape)} do not agree")
+    if not fp8_index_dim_ok(q.shape[1]):
+        raise ValueError("the fp8 index serves dim % 32 == 0 and dim <= 1024, "
+                         f"got {q.shape[1]}")
+    k = int(k)
+    if not 1 <= k <= _FP8_INDEX_KMAX:
+        raise ValueError(f"k must be in [1, {_FP8_INDEX_KMAX}], got {k}")
+    if _on_gpu(q):
+        vals, rows = _require_hip().cosine_topk_fp8(q, codes, scales, k)
+        return vals, rows
+    return torch_ref.cosine_topk_fp8(q, codes, scales, k)
+
+
+def cosine_topk_fp8_plan(n_rows: int) -> tuple[int, int, int]:
+    """(scan blocks, rows per block chunk, candidate places per query) of
+    ops.cosine_topk_fp8 over n_rows rows on the current GPU."""
+    return tuple(_require_hip().cosine_topk_fp8_plan(int(n_rows)))
+
+
 def cosine_scores(q, mat):
     """Hand wave-per-row scan (LDS-staged queries); B*D*4 must fit in LDS."""
     if _on_gpu(q, mat):
@@ -1012,6 +1060,6 @@ def gemm_bf16(a, b):
 
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_verify", "ngram_draft", "spec_accept", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
-    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk",
+    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

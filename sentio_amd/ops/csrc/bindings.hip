@@ -515,6 +515,48 @@ torch::Tensor cosine_scores(torch::Tensor q, torch::Tensor mat) {
   return scores;
 }
 
+// (scan blocks, rows per block chunk, candidate places per query) for N rows
+std::tuple<int, int, int> cosine_topk_fp8_plan(long N) {
+  int blocks = 0, chunk = 0, cap = 0;
+  check_hip(sentio_cosine_topk_fp8_plan(N, &blocks, &chunk, &cap),
+            "cosine_topk_fp8_plan");
+  return {blocks, chunk, cap};
+}
+
+// Fused fp8 index scan + top-k; the Python wrapper has checked the
+// arguments.  No host sync: the workspace comes from the caching allocator.
+std::vector<torch::Tensor> cosine_topk_fp8(torch::Tensor q, torch::Tensor codes,
+                                           torch::Tensor scales, int64_t k) {
+  TORCH_CHECK(q.is_cuda() && codes.is_cuda() && scales.is_cuda(),
+              "cosine_topk_fp8: tensors must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kHalf && q.dim() == 2 &&
+              q.is_contiguous(), "q must be contiguous fp16 [B, D]");
+  TORCH_CHECK(codes.scalar_type() == torch::kByte && codes.dim() == 2 &&
+              codes.is_contiguous() && codes.size(1) == q.size(1),
+              "codes must be contiguous uint8 [N, D]");
+  TORCH_CHECK(scales.scalar_type() == torch::kFloat && scales.dim() == 1 &&
+              scales.is_contiguous() && scales.size(0) == codes.size(0),
+              "scales must be contiguous fp32 [N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "q and codes must be 16-byte aligned");
+  const long N = codes.size(0), B = q.size(0);
+  const int D = (int)q.size(1);
+  TORCH_CHECK(N >= 1 && B >= 1 && k >= 1, "cosine_topk_fp8: empty input");
+  const int blocks = std::get<0>(cosine_topk_fp8_plan(N));
+  auto ws_s = torch::empty({B, blocks, k}, scales.options());
+  auto ws_r = torch::empty({B, blocks, k}, scales.options().dtype(torch::kInt));
+  auto out_s = torch::empty({B, k}, scales.options());
+  auto out_r = torch::empty({B, k}, scales.options().dtype(torch::kLong));
+  check_hip(sentio_cosine_topk_fp8(
+                q.data_ptr(), codes.data_ptr(), scales.data_ptr<float>(),
+                ws_s.data_ptr<float>(), ws_r.data_ptr<int>(),
+                out_s.data_ptr<float>(), (long*)out_r.data_ptr<int64_t>(), N,
+                D, (int)B, (int)k, blocks, stream()),
+            "cosine_topk_fp8");
+  return {out_s, out_r};
+}
+
 torch::Tensor bm25_score(torch::Tensor term_ids, torch::Tensor indptr,
                          torch::Tensor post_doc, torch::Tensor post_tf,
                          torch::Tensor idf, torch::Tensor doc_len,
@@ -997,6 +1039,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_constrained", &sample_constrained);
   m.def("sample_slots_constrained", &sample_slots_constrained);
   m.def("cosine_scores", &cosine_scores);
+  m.def("cosine_topk_fp8", &cosine_topk_fp8);
+  m.def("cosine_topk_fp8_plan", &cosine_topk_fp8_plan);
   m.def("bm25_score", &bm25_score);
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_cache", &flash_attn_cache);

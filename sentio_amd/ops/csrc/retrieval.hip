@@ -225,7 +225,478 @@ __global__ void fuse_topk_kernel(
   }
 }
 
+// ------------------------------------------- fp8 dense index: scan + top-k
+// The opt-in e4m3fn index (index/dense.py): codes uint8 [N, D], one fp32
+// scale per row, fp16 queries.  score[b, n] = scales[n] * sum_d q[b, d] *
+// float(code[n, d]); top-k by score descending, ties to the lower row.  No
+// [B, N] score matrix exists: selection happens inside the scan.
+//
+// Scan kernel, persistent grid (one 8-wave block per CU, at most
+// IDX_MAX_BLOCKS).  A block walks 128-row chunks, chunk = blockIdx.x +
+// i * gridDim.x; wave w takes the chunk's 16-row tile w.  Index rows are
+// the B operand of mfma_f32_16x16x32_f16 (column = lane & 15), queries the
+// A operand, so lane l ends a tile with the scores of queries (l>>4)*4 + r
+// (r = 0..3, per 16-query tile) against index row l & 15, and needs one
+// scale.  The contraction order is free, so the k axis is permuted for wide
+// loads: lane group g = l >> 4 loads the 16 bytes [u*64 + g*16, +16) of its
+// row per 64-wide unit u (four lanes cover 64 contiguous bytes; two
+// consecutive loads a 128 B line) and feeds bytes 0..7 to MFMA step 2u and
+// bytes 8..15 to step 2u+1; a D % 64 == 32 tail is one 8-byte step.  Bytes
+// become f16 in registers with v_cvt_scalef32_pk_f16_fp8 at scale 1.0
+// (exact: every e4m3fn value is an f16 value), one instruction per two
+// codes.  Queries are staged once per block in LDS in that same fragment
+// order (step, query tile, lane: one conflict-free 16 B read per MFMA); at
+// D = 1024 the 32-query fragments alone would be 256 registers per lane.
+// QT (16-query tiles, 1 or 2) is a template constant, so B <= 16 runs half
+// the MFMAs and LDS reads.  NU_CT = 16 is D = 1024 with the whole tile in
+// registers and the next chunk's loads issued ahead of the MFMAs and the
+// selection; NU_CT = 0 is any other D, streamed four units at a time.
+//
+// Selection.  Per query the block keeps in LDS a list of IDX_CAP (score,
+// row) places, its fill count and a threshold (-inf until k candidates
+// exist, then the k-th best score so far).  A lane whose score is >= the
+// threshold (>=: an equal score with a lower row must still win) appends
+// with one LDS atomic.  After every chunk, between two barriers, wave w
+// compacts the lists of queries w, w+8, .. that could overflow in the next
+// chunk (more than IDX_CAP - 128 entries): every entry's rank under (score
+// desc, row asc) is counted against the list, ranks below k move to place
+// rank (the list comes out sorted), the threshold becomes the score at
+// rank k-1.  A chunk appends at most 128 entries per query and a compacted
+// list holds at most k <= 128, so an append never runs past IDX_CAP.  A
+// block ends by compacting every list and writing k places per query to
+// the workspace [B, blocks, k], (-inf, -1) past the fill count.
+//
+// Merge kernel, one 1024-thread block per query over its blocks * k
+// places: (score, row) packs into one 64-bit key whose unsigned order is
+// the result order, an 8-bit radix select finds the k-th key in 8 passes,
+// the <= 128 keys at or above it are ranked against each other and written
+// in order.
+#define IDX_WAVES 8
+#define IDX_CHUNK (IDX_WAVES * 16)   // rows per block iteration
+#define IDX_CAP 256                  // list places per query
+#define IDX_KMAX 128
+#define IDX_MAX_BLOCKS 256
+#define IDX_MERGE_THREADS 1024
+// fp32 VALU work stays on the scalar forms, as in verify_attn_kernel and
+// for the reason given there (attention.hip, VER_NO_PK_F32)
+#define IDX_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+// 8 e4m3fn bytes (two dwords, byte j = element j) -> 8 f16, exact
+__device__ __forceinline__ f16x8_t idx_cvt8(unsigned lo, unsigned hi) {
+  const f16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)lo, 1.f, false);
+  const f16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)lo, 1.f, true);
+  const f16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)hi, 1.f, false);
+  const f16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)hi, 1.f, true);
+  const f16x4_t ab = __builtin_shufflevector(a, b, 0, 1, 2, 3);
+  const f16x4_t cd = __builtin_shufflevector(c, d, 0, 1, 2, 3);
+  return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// first k index of MFMA step s for lane group g (NU whole 64-wide units)
+__device__ __forceinline__ int idx_kbase(int s, int g, int NU) {
+  return s < 2 * NU ? (s >> 1) * 64 + g * 16 + (s & 1) * 8 : s * 32 + g * 8;
+}
+
+// one MFMA step: 8 codes of this lane's row against QT query tiles; qf is
+// the staged fragments already offset by lane * 16
+template <int QT>
+__device__ __forceinline__ void idx_step(f32x4 (&acc)[QT], const char* qf,
+                                         int s, unsigned lo, unsigned hi) {
+  const f16x8_t b = idx_cvt8(lo, hi);
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    const f16x8_t a =
+        *reinterpret_cast<const f16x8_t*>(qf + (s * QT + t) * (WAVE * 16));
+    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc[t], 0, 0, 0);
+  }
+}
+
+// wave-wide: sort one query's list by (score desc, row asc), keep the best
+// k, set the threshold once k exist.  Returns the new fill count.
+__device__ __forceinline__ int idx_compact(float* cs, int* cr, int* cnt,
+                                           float* thr, int k, int lane) {
+  const int n = min(*cnt, IDX_CAP);
+  constexpr int PER = IDX_CAP / WAVE;
+  float s[PER];
+  int r[PER], rank[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int e = lane + i * WAVE;
+    s[i] = e < n ? cs[e] : -INFINITY;
+    r[i] = e < n ? cr[e] : 0x7fffffff;
+    rank[i] = 0;
+  }
+  for (int j = 0; j < n; ++j) {
+    const float sj = cs[j];
+    const int rj = cr[j];
+#pragma unroll
+    for (int i = 0; i < PER; ++i)
+      rank[i] += (sj > s[i] || (sj == s[i] && rj < r[i])) ? 1 : 0;
+  }
+  // every lane's ranks depend on all of the reads above and a wave's LDS
+  // operations complete in order: the moves below cannot pass them
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    if (lane + i * WAVE < n && rank[i] < k) {
+      cs[rank[i]] = s[i];
+      cr[rank[i]] = r[i];
+      if (rank[i] == k - 1) *thr = s[i];
+    }
+  }
+  const int kept = min(n, k);
+  if (lane == 0) *cnt = kept;
+  __builtin_amdgcn_wave_barrier();
+  return kept;
+}
+
+template <int QT, int NU_CT>
+__launch_bounds__(IDX_WAVES * WAVE)
+IDX_NO_PK_F32 __global__ void index_scan_fp8_kernel(
+    const unsigned char* __restrict__ codes, const float* __restrict__ scales,
+    const _Float16* __restrict__ q, float* __restrict__ ws_s,
+    int* __restrict__ ws_r, long N, int D, int Bg, int k, int qbase) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int NS = D / 32;                       // MFMA steps of a row
+  const int NU = NU_CT ? NU_CT : D / 64;       // whole 64-wide units
+  char* qfrag = smem;                          // [NS][QT][64 lanes] x 16 B
+  float* cand_s = reinterpret_cast<float*>(smem + (size_t)NS * QT * WAVE * 16);
+  int* cand_r = reinterpret_cast<int*>(cand_s + QT * 16 * IDX_CAP);
+  int* cnt = cand_r + QT * 16 * IDX_CAP;       // [QT*16]
+  float* thr = reinterpret_cast<float*>(cnt + QT * 16);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int w = tid / WAVE;
+  const int c = lane & 15, g = lane >> 4;
+
+  for (int i = tid; i < NS * QT * WAVE; i += IDX_WAVES * WAVE) {
+    const int l = i & (WAVE - 1);
+    const int t = (i / WAVE) % QT, s = (i / WAVE) / QT;
+    const int qi = t * 16 + (l & 15);
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (qi < Bg)
+      v = *reinterpret_cast<const u32x4_t*>(q + (long)qi * D +
+                                            idx_kbase(s, l >> 4, NU));
+    *reinterpret_cast<u32x4_t*>(qfrag + (long)i * 16) = v;
+  }
+  if (tid < QT * 16) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+  }
+  __syncthreads();
+
+  const char* qf = qfrag + lane * 16;
+  const long nchunks = (N + IDX_CHUNK - 1) / IDX_CHUNK;
+  // this lane's row of a chunk, clamped: rows at or past N load row N-1 and
+  // are dropped at the append
+  // (both lambdas must inline: a call would put acc and the captures in
+  // scratch)
+  auto row_ptr = [&](long chunk) __attribute__((always_inline)) {
+    long row = chunk * IDX_CHUNK + w * 16 + c;
+    if (row > N - 1) row = N - 1;
+    return codes + row * (long)D;
+  };
+  // scale, append, then compact what the next chunk could overflow
+  auto finish = [&](long chunk, const f32x4 (&acc)[QT])
+                    __attribute__((always_inline)) {
+    const long row = chunk * IDX_CHUNK + w * 16 + c;
+    const bool ok = row < N;
+    const float sc = scales[ok ? row : N - 1];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qi = t * 16 + g * 4 + r;
+        const float s = acc[t][r] * sc;
+        if (ok && qi < Bg && s >= thr[qi]) {
+          const int pos = atomicAdd(&cnt[qi], 1);
+          if (pos < IDX_CAP) {
+            cand_s[qi * IDX_CAP + pos] = s;
+            cand_r[qi * IDX_CAP + pos] = (int)row;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int qi = w; qi < Bg; qi += IDX_WAVES)
+      if (cnt[qi] > IDX_CAP - IDX_CHUNK)
+        idx_compact(cand_s + qi * IDX_CAP, cand_r + qi * IDX_CAP, cnt + qi,
+                    thr + qi, k, lane);
+    __syncthreads();
+  };
+
+  if constexpr (NU_CT > 0) {
+    u32x4_t cur[NU_CT];
+    if ((long)blockIdx.x < nchunks) {
+      const unsigned char* rp = row_ptr(blockIdx.x) + g * 16;
+#pragma unroll
+      for (int u = 0; u < NU_CT; ++u)
+        cur[u] = __builtin_nontemporal_load(
+            reinterpret_cast<const u32x4_t*>(rp + u * 64));
+    }
+    for (long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+      u32x4_t nxt[NU_CT];
+#pragma unroll
+      for (int u = 0; u < NU_CT; ++u) nxt[u] = cur[u];
+      if (chunk + gridDim.x < nchunks) {
+        const unsigned char* rp = row_ptr(chunk + gridDim.x) + g * 16;
+#pragma unroll
+        for (int u = 0; u < NU_CT; ++u)
+          nxt[u] = __builtin_nontemporal_load(
+              reinterpret_cast<const u32x4_t*>(rp + u * 64));
+      }
+      f32x4 acc[QT];
+#pragma unroll
+      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < NU_CT; ++u) {
+        idx_step<QT>(acc, qf, 2 * u, cur[u].x, cur[u].y);
+        idx_step<QT>(acc, qf, 2 * u + 1, cur[u].z, cur[u].w);
+      }
+      finish(chunk, acc);
+#pragma unroll
+      for (int u = 0; u < NU_CT; ++u) cur[u] = nxt[u];
+    }
+  } else {
+    for (long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+      const unsigned char* rb = row_ptr(chunk);
+      f32x4 acc[QT];
+#pragma unroll
+      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int u0 = 0; u0 < NU; u0 += 4) {
+        u32x4_t raw[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          raw[i] = u32x4_t{0u, 0u, 0u, 0u};
+          if (u0 + i < NU)
+            raw[i] = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4_t*>(rb + (u0 + i) * 64 + g * 16));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (u0 + i < NU) {
+            idx_step<QT>(acc, qf, 2 * (u0 + i), raw[i].x, raw[i].y);
+            idx_step<QT>(acc, qf, 2 * (u0 + i) + 1, raw[i].z, raw[i].w);
+          }
+        }
+      }
+      if (D & 32) {
+        const u32x2_t tl = __builtin_nontemporal_load(
+            reinterpret_cast<const u32x2_t*>(rb + (NS - 1) * 32 + g * 8));
+        idx_step<QT>(acc, qf, NS - 1, tl.x, tl.y);
+      }
+      finish(chunk, acc);
+    }
+  }
+
+  for (int qi = w; qi < Bg; qi += IDX_WAVES) {
+    float* cs = cand_s + qi * IDX_CAP;
+    int* cr = cand_r + qi * IDX_CAP;
+    const int n = idx_compact(cs, cr, cnt + qi, thr + qi, k, lane);
+    const long base = ((long)(qbase + qi) * gridDim.x + blockIdx.x) * k;
+    for (int i = lane; i < k; i += WAVE) {
+      ws_s[base + i] = i < n ? cs[i] : -INFINITY;
+      ws_r[base + i] = i < n ? cr[i] : -1;
+    }
+  }
+}
+
+// (score, row) -> key: larger key = earlier in the result.  Row -1 (an empty
+// place) never enters: the merge skips it.
+__device__ __forceinline__ unsigned long long idx_key(float s, int r) {
+  unsigned u = __float_as_uint(s);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned)~r;
+}
+
+// wave-uniform call: one LDS atomic per distinct digit in the wave (the top
+// bytes of the keys of one query are nearly all equal)
+__device__ __forceinline__ void idx_hist_add(int* hist, bool on, int digit,
+                                             int lane) {
+  unsigned long long todo = __ballot(on);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int d0 = __shfl(digit, leader, WAVE);
+    const unsigned long long same = __ballot(on && digit == d0);
+    if (lane == leader) atomicAdd(&hist[d0], (int)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+__launch_bounds__(IDX_MERGE_THREADS)
+IDX_NO_PK_F32 __global__ void index_merge_kernel(
+    const float* __restrict__ ws_s, const int* __restrict__ ws_r,
+    float* __restrict__ out_s, long* __restrict__ out_r, int n, int k) {
+  __shared__ int hist[256];
+  __shared__ unsigned long long sel[IDX_KMAX];
+  __shared__ int sh_valid, sh_nsel, sh_digit, sh_want;
+  const float* cs = ws_s + (long)blockIdx.x * n;
+  const int* cr = ws_r + (long)blockIdx.x * n;
+  float* os = out_s + (long)blockIdx.x * k;
+  long* orow = out_r + (long)blockIdx.x * k;
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+
+  if (tid == 0) {
+    sh_valid = 0;
+    sh_nsel = 0;
+  }
+  __syncthreads();
+  int v = 0;
+  for (int i = tid; i < n; i += IDX_MERGE_THREADS) v += cr[i] >= 0 ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+  if (lane == 0 && v) atomicAdd(&sh_valid, v);
+  __syncthreads();
+  const int kk = min(k, sh_valid);
+
+  if (kk > 0) {
+    // radix select of the kk-th largest key, one byte per pass from the top
+    unsigned long long prefix = 0, mask = 0;
+    int want = kk;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for (int i0 = 0; i0 < n; i0 += IDX_MERGE_THREADS) {
+        const int i = i0 + tid;
+        const int r = i < n ? cr[i] : -1;
+        const unsigned long long key = r >= 0 ? idx_key(cs[i], r) : 0;
+        idx_hist_add(hist, r >= 0 && (key & mask) == prefix,
+                     (int)((key >> shift) & 255), lane);
+      }
+      __syncthreads();
+      if (tid < WAVE) {
+        // lane l owns digits 4l .. 4l+3; above = keys in higher lanes' digits
+        int cbin[4];
+        int sum = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          cbin[b] = hist[4 * lane + b];
+          sum += cbin[b];
+        }
+        int suf = sum;
+        for (int off = 1; off < WAVE; off <<= 1) {
+          const int o = __shfl_down(suf, off, WAVE);
+          if (lane + off < WAVE) suf += o;
+        }
+        int above = suf - sum;
+#pragma unroll
+        for (int b = 3; b >= 0; --b) {
+          if (above < want && want <= above + cbin[b]) {
+            sh_digit = 4 * lane + b;
+            sh_want = want - above;
+          }
+          above += cbin[b];
+        }
+      }
+      __syncthreads();
+      prefix |= (unsigned long long)sh_digit << shift;
+      mask |= 255ull << shift;
+      want = sh_want;
+    }
+    // keys are distinct (rows are), so exactly kk keys are >= the kk-th
+    for (int i = tid; i < n; i += IDX_MERGE_THREADS) {
+      const int r = cr[i];
+      if (r < 0) continue;
+      const unsigned long long key = idx_key(cs[i], r);
+      if (key >= prefix) {
+        const int p = atomicAdd(&sh_nsel, 1);
+        if (p < IDX_KMAX) sel[p] = key;
+      }
+    }
+    __syncthreads();
+    if (tid < kk) {
+      const unsigned long long me = sel[tid];
+      int rank = 0;
+      for (int j = 0; j < kk; ++j) rank += sel[j] > me ? 1 : 0;
+      unsigned u = (unsigned)(me >> 32);
+      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+      os[rank] = __uint_as_float(u);
+      orow[rank] = (long)(int)~(unsigned)me;
+    }
+  }
+  for (int i = kk + tid; i < k; i += IDX_MERGE_THREADS) {
+    os[i] = -INFINITY;
+    orow[i] = -1;
+  }
+}
+
+template <int QT, int NU_CT>
+static hipError_t launch_index_scan(const void* q, const void* codes,
+                                    const float* scales, float* ws_s,
+                                    int* ws_r, long N, int D, int Bg, int k,
+                                    int qbase, int blocks,
+                                    hipStream_t stream) {
+  const size_t lds = (size_t)(D / 32) * QT * WAVE * 16 +
+                     (size_t)QT * 16 * (IDX_CAP * 8 + 8);
+  auto kern = index_scan_fp8_kernel<QT, NU_CT>;
+  hipError_t e = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(kern),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(IDX_WAVES * WAVE), lds,
+                     stream, (const unsigned char*)codes, scales,
+                     (const _Float16*)q, ws_s, ws_r, N, D, Bg, k, qbase);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
 extern "C" {
+
+hipError_t sentio_cosine_topk_fp8_plan(long N, int* blocks, int* chunk_rows,
+                                       int* cap) {
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return e;
+  if (N < 1 || cus < 1) return hipErrorInvalidValue;
+  const long chunks = (N + IDX_CHUNK - 1) / IDX_CHUNK;
+  long b = cus < IDX_MAX_BLOCKS ? cus : IDX_MAX_BLOCKS;
+  if (b > chunks) b = chunks;
+  *blocks = (int)b;
+  *chunk_rows = IDX_CHUNK;
+  *cap = IDX_CAP;
+  return hipSuccess;
+}
+
+hipError_t sentio_cosine_topk_fp8(const void* q, const void* codes,
+                                  const float* scales, float* ws_s, int* ws_r,
+                                  float* out_s, long* out_r, long N, int D,
+                                  int B, int k, int blocks,
+                                  hipStream_t stream) {
+  if (N < 1 || N > 0x7fffffffL || D < 32 || D > 1024 || D % 32 || B < 1 ||
+      k < 1 || k > IDX_KMAX || blocks < 1 || blocks > IDX_MAX_BLOCKS)
+    return hipErrorInvalidValue;
+  for (int b0 = 0; b0 < B; b0 += 32) {
+    const int Bg = B - b0 < 32 ? B - b0 : 32;
+    const void* qg = (const char*)q + (size_t)b0 * D * 2;
+    hipError_t e;
+    if (D == 1024)
+      e = Bg > 16 ? launch_index_scan<2, 16>(qg, codes, scales, ws_s, ws_r, N,
+                                             D, Bg, k, b0, blocks, stream)
+                  : launch_index_scan<1, 16>(qg, codes, scales, ws_s, ws_r, N,
+                                             D, Bg, k, b0, blocks, stream);
+    else
+      e = Bg > 16 ? launch_index_scan<2, 0>(qg, codes, scales, ws_s, ws_r, N,
+                                            D, Bg, k, b0, blocks, stream)
+                  : launch_index_scan<1, 0>(qg, codes, scales, ws_s, ws_r, N,
+                                            D, Bg, k, b0, blocks, stream);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)B),
+                     dim3(IDX_MERGE_THREADS), 0, stream, ws_s, ws_r, out_s,
+                     out_r, blocks * k, k);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 hipError_t sentio_cosine_scores_f16(const void* mat, const void* q,
                                     float* scores, long N, int D, int B,

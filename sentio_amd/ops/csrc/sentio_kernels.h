@@ -124,6 +124,22 @@ hipError_t sentio_cosine_scores_f16(const void* mat, const void* q,
 hipError_t sentio_cosine_scores_bf16(const void* mat, const void* q,
                                      float* scores, long N, int D, int B,
                                      hipStream_t stream);
+// launch plan of sentio_cosine_topk_fp8 on the current device for N rows:
+// scan blocks (one per CU, at most 256, at most one per chunk), rows per
+// block chunk, places per query in a block's candidate list
+hipError_t sentio_cosine_topk_fp8_plan(long N, int* blocks, int* chunk_rows,
+                                       int* cap);
+// queries first here: q fp16 [B, D], codes uint8 (e4m3fn) [N, D], scales
+// fp32 [N]; ws_s / ws_r hold B * blocks * k places; out_s f32 / out_r i64
+// [B, k], sorted by (score desc, row asc), (-inf, -1) past N; dims are (N,
+// D, B, k, blocks).  hipErrorInvalidValue unless D % 32 == 0, 32 <= D <=
+// 1024, 1 <= k <= 128, N < 2^31 and 1 <= blocks <= 256.  q and codes must
+// be 16-byte aligned
+hipError_t sentio_cosine_topk_fp8(const void* q, const void* codes,
+                                  const float* scales, float* ws_s, int* ws_r,
+                                  float* out_s, long* out_r, long N, int D,
+                                  int B, int k, int blocks,
+                                  hipStream_t stream);
 hipError_t sentio_bm25(const long* term_ids, const long* qoff,
                        const long* starts, const int* post_doc,
                        const float* post_tf, const float* idf,

@@ -177,6 +177,37 @@ def cosine_topk(
     return torch.topk(scores, k, dim=1)
 
 
+def index_quantize(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The fp8 dense index's quantisation spec.  x fp32 [N, D], rows
+    L2-normalised: scale = max(max|x|, 2**-20) / 448 per row, code =
+    RNE_e4m3fn(clamp(x * (1 / scale), ±448)).  Returns (codes uint8 [N, D],
+    scales fp32 [N]); a row's value is code * scale."""
+    x = x.float()
+    scale = x.abs().amax(dim=1).clamp_min(2.0 ** -20) / 448.0
+    codes = (x * (1.0 / scale).unsqueeze(1)).clamp(-448.0, 448.0) \
+        .to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, scale
+
+
+def cosine_topk_fp8(
+    q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, k: int
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The fp8 index's scoring spec: score[b, n] = scales[n] * sum_d q[b, d]
+    * float(code[n, d]); top-k by score descending, ties to the lower row,
+    padded with (-inf, -1) when k > N.  Returns (scores [B,k] fp32, rows
+    [B,k] int64)."""
+    B, N = q.shape[0], codes.shape[0]
+    scores = (q.float() @ codes.view(torch.float8_e4m3fn).float().T) \
+        * scales.float()
+    order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+    rows = order[:, :k]
+    vals = torch.gather(scores, 1, rows)
+    if k > N:
+        vals = torch.cat([vals, vals.new_full((B, k - N), float("-inf"))], 1)
+        rows = torch.cat([rows, rows.new_full((B, k - N), -1)], 1)
+    return vals, rows
+
+
 def bm25_score(
     term_ids: torch.Tensor,
     indptr: torch.Tensor,

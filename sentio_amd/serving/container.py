@@ -137,7 +137,8 @@ class ServiceContainer:
     def dense_index(self) -> DenseIndex:
         return self._get("dense_index", lambda: DenseIndex(
             dim=self.settings.embedding_dim, device=self.device,
-            dtype=torch.float16))
+            dtype="fp8" if self.settings.dense_index_dtype == "fp8"
+            else torch.float16))
 
     def bm25_index(self) -> BM25Index:
         return self._get("bm25_index", lambda: BM25Index(
