@@ -6,6 +6,11 @@ Run: python scripts/dense_index_probe.py            (every step, each in a
                                                      child with a time limit)
      python scripts/dense_index_probe.py time N     (N rows, dim 1024)
      python scripts/dense_index_probe.py recall     (N = 1M, 256 queries)
+     python scripts/dense_index_probe.py --mask [N] (filtered search: the
+         masked scan, ops.cosine_topk_masked, at B = 32, k = 10 over both
+         index types beside the unfiltered search of each; HIP-event medians
+         per call, the variants alternating inside every repeat; not part of
+         the default steps)
 TB/s counts each path's own index bytes: N * 2048 (fp16) or N * 1028 (fp8)."""
 import os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -76,6 +81,63 @@ def time_probe(n, repeats=3):
                       + f" ms  {nbytes / min(ts) / 1e12:.2f} TB/s")
 
 
+def event_median(fn, iters):
+    """Median HIP-event time of one call, in seconds."""
+    for _ in range(3):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True),
+           torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return sorted(a.elapsed_time(b) for a, b in ev)[iters // 2] / 1e3
+
+
+def mask_probe(n, repeats=3, B=32, k=10, run=1024):
+    """Allowed fractions 1, 0.1 and 0.01, as random bits and as contiguous
+    runs of `run` rows (documents ingested tenant by tenant)."""
+    from sentio_amd import ops
+
+    dev = "cuda:0"
+    mat, codes, scales = build(n, 0, dev)
+    q = unit_rows(B, 1, dev).half()
+    g = torch.Generator(device=dev).manual_seed(2)
+    masks = {"all ones": torch.ones(n, dtype=torch.bool, device=dev)}
+    for frac in (0.1, 0.01):
+        masks[f"{frac:.0%} random"] = torch.rand(n, generator=g,
+                                                 device=dev) < frac
+        runs = torch.rand((n + run - 1) // run, generator=g, device=dev) < frac
+        masks[f"{frac:.0%} runs of {run}"] = runs.repeat_interleave(run)[:n]
+    allow = {name: ops.pack_row_mask(m[None]) for name, m in masks.items()}
+    iters = max(20, min(200, 200_000_000 // n))
+    print(f"--- masked scan, N={n} dim={DIM} B={B} k={k}: median of {iters} "
+          f"event-timed calls, {repeats} repeats, scan blocks "
+          f"{ops.cosine_topk_fp8_plan(n)[0]}")
+    variants = [("fp16 gemm+topk, unfiltered",
+                 lambda: ops.cosine_topk(q, mat, k)),
+                ("fp8 fused scan, unfiltered",
+                 lambda: ops.cosine_topk_fp8(q, codes, scales, k))]
+    for name, a in allow.items():
+        variants.append((f"fp16 masked, {name}", lambda a=a:
+                         ops.cosine_topk_masked(q, mat, None, k, a)))
+        variants.append((f"fp8 masked, {name}", lambda a=a:
+                         ops.cosine_topk_masked(q, codes, scales, k, a)))
+    times = {name: [] for name, _ in variants}
+    for _ in range(repeats):
+        for name, fn in variants:
+            times[name].append(event_median(fn, iters))
+    for name, m in masks.items():
+        print(f"mask {name}: {int(m.sum())} rows allowed")
+    for name, ts in times.items():
+        print(f"{name:34s} " + " ".join(f"{t * 1e3:8.3f}" for t in ts) + " ms")
+    # the timed calls must agree with the unfiltered search where they can
+    r8 = ops.cosine_topk_masked(q, codes, scales, k, allow["all ones"])[1]
+    print("fp8 all-ones rows == unfiltered rows:",
+          torch.equal(r8, ops.cosine_topk_fp8(q, codes, scales, k)[1]))
+
+
 def recall_probe(n=1_000_000, nq=256):
     from sentio_amd import ops
 
@@ -107,7 +169,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if not torch.cuda.is_available():
         sys.exit(f"{__file__}: needs a GPU (MI355X)")
-    if sys.argv[1] == "time":
+    if sys.argv[1] == "--mask":
+        mask_probe(int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000)
+    elif sys.argv[1] == "time":
         time_probe(int(sys.argv[2]))
     elif sys.argv[1] == "recall":
         recall_probe()

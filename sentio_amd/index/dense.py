@@ -16,6 +16,13 @@ dtype="fp8" (opt-in) stores e4m3fn codes with one fp32 scale per row instead
 (dim + 4 bytes per document against 2 * dim; torch_ref.index_quantize is the
 spec) and searches with ops.cosine_topk_fp8, a fused scan + top-k kernel
 that writes no [B, N] score matrix.
+
+filter_mode="exact" (opt-in) turns search(metadata_filter=...) from an
+over-fetch of top_k * 4 hits filtered on the host into an exact filtered
+search: the filter becomes a row bit mask (built on the host from the
+payloads, cached per filter, extended as rows are added) and
+ops.cosine_topk_masked selects top_k among the allowed rows only.
+search_rows(allow=...) takes such masks directly, one per query if wanted.
 """
 
 from __future__ import annotations
@@ -36,7 +43,13 @@ class DenseIndex:
         dim: int = 1024,
         device: str = "cpu",
         dtype: torch.dtype | str = torch.float16,
+        filter_mode: str = "post",
     ) -> None:
+        if filter_mode not in ("post", "exact"):
+            raise ValueError(f"unknown filter_mode {filter_mode!r}")
+        self.filter_mode = filter_mode
+        # filter key -> [host bool rows, rows covered, packed device mask]
+        self._masks: dict[str, list] = {}
         self.dim = dim
         self.device = device
         self.fp8 = dtype in ("fp8", torch.float8_e4m3fn)
@@ -132,6 +145,14 @@ class DenseIndex:
             query = query.unsqueeze(0)
         if self._size == 0:
             return [[] for _ in range(query.shape[0])]
+        if metadata_filter and self.filter_mode == "exact":
+            q = query.to(self.device, torch.float32)
+            q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
+            vals, idx = self._topk_masked(q, top_k,
+                                          self._filter_mask(metadata_filter))
+            return [[(self.doc_ids[i], float(v)) for v, i in zip(vr, ir)
+                     if i >= 0]
+                    for vr, ir in zip(vals.cpu().tolist(), idx.cpu().tolist())]
         fetch_k = min(top_k * 4, self._size) if metadata_filter else top_k
         k = min(fetch_k, self._size)
         q = query.to(self.device, torch.float32)
@@ -161,12 +182,16 @@ class DenseIndex:
             out.append(hits)
         return out
 
-    def search_rows(self, query: torch.Tensor, top_k: int
+    def search_rows(self, query: torch.Tensor, top_k: int,
+                    allow: torch.Tensor | None = None
                     ) -> tuple[torch.Tensor, torch.Tensor]:
         """Tensor-only batched cosine top-k: (scores [B,k] f32, rows [B,k]
         i64), padded with (-inf, -1) when the shard holds fewer than top_k
         rows.  NO host sync — the multi-GPU merge all-gathers these tensors
-        directly (no pickled objects on the query hot path)."""
+        directly (no pickled objects on the query hot path).
+        allow: int32 [1 or B, W] row mask on the index device
+        (ops.pack_row_mask), one for all queries or one per query: the
+        search runs over the allowed rows only, in either filter_mode."""
         if query.ndim == 1:
             query = query.unsqueeze(0)
         B = query.shape[0]
@@ -177,6 +202,8 @@ class DenseIndex:
         k = min(top_k, self._size)
         q = query.to(self.device, torch.float32)
         q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        if allow is not None:
+            return self._topk_masked(q, top_k, allow)
         if self.fp8:
             vals, idx = self._topk_fp8(q, k)
         elif self.device != "cpu":
@@ -209,6 +236,56 @@ class DenseIndex:
                                    self._codes[: self._size],
                                    self._scales[: self._size], k)
 
+    MASK_CACHE = 16
+
+    def _topk_masked(self, q: torch.Tensor, k: int, allow: torch.Tensor
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+        """The k best allowed rows for normalised fp32 queries, padded with
+        (-inf, -1).  The masked scan kernel serves GPU fp8 and fp16 indexes
+        at dim % 32 == 0, dim <= 1024 and k <= 128; any other shape and the
+        CPU take the reference."""
+        from sentio_amd import ops
+        from sentio_amd.ops import torch_ref
+
+        n = self._size
+        if allow.dtype != torch.int32 or allow.dim() != 2 or \
+                allow.shape[0] not in (1, q.shape[0]) or \
+                allow.shape[1] != 4 * ((n + 127) // 128) or \
+                allow.device != q.device:
+            raise ValueError(f"allow must be int32 [1 or {q.shape[0]}, "
+                             f"{4 * ((n + 127) // 128)}] on {q.device}")
+        rows = self._codes[:n] if self.fp8 else self._vecs[:n]
+        scales = self._scales[:n] if self.fp8 else None
+        if self.device != "cpu" and ops.fp8_index_dim_ok(self.dim) \
+                and k <= 128 and (self.fp8 or self.dtype == torch.float16):
+            return ops.cosine_topk_masked(q.to(torch.float16), rows, scales,
+                                          k, allow.contiguous())
+        qq = q.to(torch.float16) if self.fp8 else q
+        return torch_ref.cosine_topk_masked(qq, rows, scales, k, allow)
+
+    def _filter_mask(self, metadata_filter: dict) -> torch.Tensor:
+        """The filter's int32 [1, W] row mask on the index device.  The
+        metadata is matched on the host once per row: a cached filter is
+        extended over the rows added since, never rebuilt."""
+        from sentio_amd.ops import torch_ref
+
+        key = repr(sorted(metadata_filter.items(), key=lambda kv: str(kv[0])))
+        with self._lock:
+            n = self._size
+            ent = self._masks.pop(key, None) or \
+                [torch.empty(0, dtype=torch.bool), 0, None]
+            if ent[1] < n:
+                new = [all(self._docs[d].metadata.get(f) == v
+                           for f, v in metadata_filter.items())
+                       for d in self.doc_ids[ent[1]:n]]
+                ent[0] = torch.cat([ent[0], torch.tensor(new, dtype=torch.bool)])
+                ent[1] = n
+                ent[2] = torch_ref.pack_row_mask(ent[0][None]).to(self.device)
+            self._masks[key] = ent               # most recently used last
+            while len(self._masks) > self.MASK_CACHE:
+                self._masks.pop(next(iter(self._masks)))
+            return ent[2]
+
     def get_document(self, doc_id: str) -> Document | None:
         return self._docs.get(doc_id)
 
@@ -228,6 +305,7 @@ class DenseIndex:
             self._size = 0
             self.doc_ids.clear()
             self._docs.clear()
+            self._masks.clear()
 
     # ----- snapshot save/load (reference had BM25 pickle + external Qdrant;
     # here the index itself persists: HBM→disk) -----
@@ -275,6 +353,8 @@ class DenseIndex:
             "dim": self.dim,
             "device": str(self.device),
             "dtype": "fp8" if self.fp8 else str(self.dtype),
+            "filter_mode": self.filter_mode,
+            "cached_filter_masks": len(self._masks),
             "hbm_bytes": (self._codes.nelement() + 4 * self._scales.nelement()
                           if self.fp8 else
                           self._vecs.element_size() * self._vecs.nelement()),

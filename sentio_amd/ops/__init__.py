@@ -590,6 +590,59 @@ def cosine_topk_fp8_plan(n_rows: int) -> tuple[int, int, int]:
     return tuple(_require_hip().cosine_topk_fp8_plan(int(n_rows)))
 
 
+def pack_row_mask(allowed):
+    """bool [..., N] -> the int32 [..., 4 * ceil(N / 128)] row mask that
+    cosine_topk_masked reads: row n is bit n & 31 of word n >> 5."""
+    return torch_ref.pack_row_mask(allowed)
+
+
+def cosine_topk_masked(q, rows, scales, k: int, allow):
+    """Exact filtered search: cosine_topk_fp8 over the rows that allow
+    permits, for both index types.  q fp16 [B, D]; rows uint8 e4m3fn codes
+    [N, D] with scales fp32 [N], or fp16 [N, D] with scales None; allow
+    int32 [M, W], M 1 (one mask for every query) or B, W = 4 * ceil(N /
+    128), row n at bit n & 31 of word n >> 5 (pack_row_mask), bits at or
+    past N ignored.  1 <= k <= 128, D % 32 == 0 and D <= 1024, any B.
+    Returns (scores f32 [B, k], rows i64 [B, k]) over the allowed rows by
+    score descending, ties to the lower row, padded with (-inf, -1)
+    (torch_ref.cosine_topk_masked is the spec and the CPU path).  The scan
+    skips every 16-row tile and every 128-row chunk in which no query allows
+    a row.  No host sync; nothing is converted or copied: a bad shape,
+    dtype, device, alignment, k or D raises ValueError before a launch."""
+    args = [("q", q, torch.float16, 2),
+            ("rows", rows, torch.float16 if scales is None else torch.uint8, 2),
+            ("allow", allow, torch.int32, 2)]
+    if scales is not None:
+        args.append(("scales", scales, torch.float32, 1))
+    for name, t, dt, nd in args:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd \
+                or t.numel() == 0 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a non-empty contiguous {dt} "
+                             f"{nd}-d tensor")
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, q on {q.device}")
+    B, N = q.shape[0], rows.shape[0]
+    if rows.shape[1] != q.shape[1] or \
+            (scales is not None and scales.shape[0] != N):
+        raise ValueError(f"q {tuple(q.shape)}, rows {tuple(rows.shape)} and "
+                         "scales do not agree")
+    if not fp8_index_dim_ok(q.shape[1]):
+        raise ValueError("the masked scan serves dim % 32 == 0 and dim <= "
+                         f"1024, got {q.shape[1]}")
+    if allow.shape[0] not in (1, B) or allow.shape[1] != 4 * ((N + 127) // 128):
+        raise ValueError(f"allow must be [1 or {B}, {4 * ((N + 127) // 128)}]"
+                         f", got {tuple(allow.shape)}")
+    if any(t.data_ptr() % 16 for t in (q, rows, allow)):
+        raise ValueError("q, rows and allow must be 16-byte aligned")
+    k = int(k)
+    if not 1 <= k <= _FP8_INDEX_KMAX:
+        raise ValueError(f"k must be in [1, {_FP8_INDEX_KMAX}], got {k}")
+    if _on_gpu(q):
+        vals, idx = _require_hip().cosine_topk_masked(q, rows, scales, k, allow)
+        return vals, idx
+    return torch_ref.cosine_topk_masked(q, rows, scales, k, allow)
+
+
 def cosine_scores(q, mat):
     """Hand wave-per-row scan (LDS-staged queries); B*D*4 must fit in LDS."""
     if _on_gpu(q, mat):
@@ -1060,6 +1113,6 @@ def gemm_bf16(a, b):
 
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_verify", "ngram_draft", "spec_accept", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
-    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok",
+    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok", "cosine_topk_masked", "pack_row_mask",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -557,6 +557,54 @@ std::vector<torch::Tensor> cosine_topk_fp8(torch::Tensor q, torch::Tensor codes,
   return {out_s, out_r};
 }
 
+// Masked scan + top-k over e4m3fn codes (scales given) or fp16 rows (no
+// scales); the Python wrapper has checked the arguments.  No host sync.
+std::vector<torch::Tensor> cosine_topk_masked(
+    torch::Tensor q, torch::Tensor rows, c10::optional<torch::Tensor> scales,
+    int64_t k, torch::Tensor allow) {
+  TORCH_CHECK(q.is_cuda() && rows.is_cuda() && allow.is_cuda() &&
+              (!scales.has_value() || scales->is_cuda()),
+              "cosine_topk_masked: tensors must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kHalf && q.dim() == 2 &&
+              q.is_contiguous(), "q must be contiguous fp16 [B, D]");
+  TORCH_CHECK(rows.scalar_type() ==
+                  (scales.has_value() ? torch::kByte : torch::kHalf) &&
+              rows.dim() == 2 && rows.is_contiguous() &&
+              rows.size(1) == q.size(1),
+              "rows must be contiguous uint8 (with scales) or fp16 [N, D]");
+  const long N = rows.size(0), B = q.size(0);
+  const int D = (int)q.size(1);
+  TORCH_CHECK(N >= 1 && B >= 1 && k >= 1, "cosine_topk_masked: empty input");
+  if (scales.has_value())
+    TORCH_CHECK(scales->scalar_type() == torch::kFloat && scales->dim() == 1 &&
+                scales->is_contiguous() && scales->size(0) == N,
+                "scales must be contiguous fp32 [N]");
+  TORCH_CHECK(allow.scalar_type() == torch::kInt && allow.dim() == 2 &&
+              allow.is_contiguous() &&
+              (allow.size(0) == 1 || allow.size(0) == B) &&
+              allow.size(1) == 4 * ((N + 127) / 128),
+              "allow must be contiguous int32 [1 or B, 4 * ceil(N / 128)]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(allow.data_ptr()) % 16 == 0,
+              "q, rows and allow must be 16-byte aligned");
+  const int blocks = std::get<0>(cosine_topk_fp8_plan(N));
+  auto f32 = q.options().dtype(torch::kFloat);
+  auto ws_s = torch::empty({B, blocks, k}, f32);
+  auto ws_r = torch::empty({B, blocks, k}, f32.dtype(torch::kInt));
+  auto out_s = torch::empty({B, k}, f32);
+  auto out_r = torch::empty({B, k}, f32.dtype(torch::kLong));
+  check_hip(sentio_cosine_topk_masked(
+                q.data_ptr(), rows.data_ptr(),
+                scales.has_value() ? scales->data_ptr<float>() : nullptr,
+                allow.data_ptr<int>(), (int)allow.size(0),
+                ws_s.data_ptr<float>(), ws_r.data_ptr<int>(),
+                out_s.data_ptr<float>(), (long*)out_r.data_ptr<int64_t>(), N,
+                D, (int)B, (int)k, blocks, stream()),
+            "cosine_topk_masked");
+  return {out_s, out_r};
+}
+
 torch::Tensor bm25_score(torch::Tensor term_ids, torch::Tensor indptr,
                          torch::Tensor post_doc, torch::Tensor post_tf,
                          torch::Tensor idf, torch::Tensor doc_len,
@@ -1041,6 +1089,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_scores", &cosine_scores);
   m.def("cosine_topk_fp8", &cosine_topk_fp8);
   m.def("cosine_topk_fp8_plan", &cosine_topk_fp8_plan);
+  m.def("cosine_topk_masked", &cosine_topk_masked);
   m.def("bm25_score", &bm25_score);
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_cache", &flash_attn_cache);

@@ -648,6 +648,345 @@ static hipError_t launch_index_scan(const void* q, const void* codes,
   return hipSuccess;
 }
 
+// ------------------------------------- masked scan: exact filtered search
+// index_scan_masked_kernel is the scan above with a row filter and a second
+// element type.  allow is int32 [M, W], M == 1 (one mask for every query) or
+// M == B; row n is bit n & 31 of word n >> 5 and W = 4 * chunks, so the bits
+// of a 128-row chunk are one aligned 16-byte group per mask.  Bits at or
+// past N are cleared as the words are read.  A row whose bit is clear never
+// appends, so the lists, the compaction, the overflow bound (a chunk still
+// appends at most 128 entries per query), the workspace and the merge are
+// those of the unmasked scan.
+//
+// A filter lets the scan read less.  A block's chunks are taken 64 at a
+// time (a window).  The block first ORs the groups of the window's chunks
+// over its queries (lane = chunk, wave = query subset, one ballot per wave
+// ORed into two LDS words) and every wave reads that 64-bit map after one
+// barrier: a chunk with no bit set costs the block nothing further, no
+// loads, no MFMAs and no barriers, and every wave walks the same map.  The
+// per-query words of the live chunk after the current one (one 16-byte
+// load by each of the first M threads) go to a ring of LDS slots before the
+// two barriers that end the current chunk, so staging adds no barrier.  The
+// append reads the bit of (query, row) from the slot; a wave ORs the slot's
+// words over the queries and, if its 16-row tile has no bit set, issues no
+// row loads and no MFMAs and appends nothing (wave-uniform).
+//
+// ET = unsigned char is the e4m3fn index (idx_cvt8, a scale per row).  ET =
+// _Float16 is the default index: a 16-byte load is 8 consecutive halves,
+// one B operand of mfma_f32_16x16x32_f16 as it stands, and the score is the
+// fp32 sum of the fp16 products.  Its query fragments are staged in that
+// order (step s, lane group g: k = s*32 + g*8).  Both stream 64-byte units,
+// four loads at a time; NU_CT = 16 (e4m3fn, D = 1024) keeps the tile in
+// registers and issues the next live chunk's loads ahead of the MFMAs.
+// That prefetch is predicated on the next chunk's words, so this variant
+// stages two live chunks ahead in a ring of three slots.  A 2048-byte fp16
+// row does not fit in registers twice, so fp16 always streams.
+template <int QT>
+__device__ __forceinline__ void idx_step16(f32x4 (&acc)[QT], const char* qf,
+                                           int s, u32x4_t raw) {
+  const f16x8_t b = __builtin_bit_cast(f16x8_t, raw);
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    const f16x8_t a =
+        *reinterpret_cast<const f16x8_t*>(qf + (s * QT + t) * (WAVE * 16));
+    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc[t], 0, 0, 0);
+  }
+}
+
+// the 16-byte group of one mask row for one chunk, bits at or past N cleared
+__device__ __forceinline__ u32x4_t idx_mask_group(const unsigned* allow_row,
+                                                  long chunk, long N) {
+  u32x4_t v = *reinterpret_cast<const u32x4_t*>(allow_row + chunk * 4);
+  const long left = N - chunk * IDX_CHUNK;      // >= 1 for a chunk of the scan
+  if (left < IDX_CHUNK) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long nv = left - 32 * j;
+      v[j] &= nv >= 32 ? 0xffffffffu : nv <= 0 ? 0u : (1u << nv) - 1u;
+    }
+  }
+  return v;
+}
+
+template <typename ET, int QT, int NU_CT>
+__launch_bounds__(IDX_WAVES * WAVE)
+IDX_NO_PK_F32 __global__ void index_scan_masked_kernel(
+    const ET* __restrict__ rows, const float* __restrict__ scales,
+    const _Float16* __restrict__ q, const unsigned* __restrict__ allow,
+    int MQ, float* __restrict__ ws_s, int* __restrict__ ws_r, long N, int D,
+    int Bg, int k, int qbase) {
+  constexpr bool F16 = sizeof(ET) == 2;
+  static_assert(!(F16 && NU_CT), "fp16 rows are streamed");
+  constexpr int NSLOT = NU_CT ? 3 : 2;         // mask slots in the ring
+  constexpr int MWS = QT * 16 * 4;             // words of a slot
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int NS = D / 32;                       // MFMA steps of a row
+  const int NU = NU_CT ? NU_CT : (F16 ? D / 32 : D / 64);   // 64-byte units
+  char* qfrag = smem;                          // [NS][QT][64 lanes] x 16 B
+  float* cand_s = reinterpret_cast<float*>(smem + (size_t)NS * QT * WAVE * 16);
+  int* cand_r = reinterpret_cast<int*>(cand_s + QT * 16 * IDX_CAP);
+  int* cnt = cand_r + QT * 16 * IDX_CAP;       // [QT*16]
+  float* thr = reinterpret_cast<float*>(cnt + QT * 16);
+  unsigned* mw = reinterpret_cast<unsigned*>(thr + QT * 16);  // [NSLOT][MWS]
+  unsigned* live = mw + NSLOT * MWS;           // [2 windows][2 words]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int w = tid / WAVE;
+  const int c = lane & 15, g = lane >> 4;
+
+  for (int i = tid; i < NS * QT * WAVE; i += IDX_WAVES * WAVE) {
+    const int l = i & (WAVE - 1);
+    const int t = (i / WAVE) % QT, s = (i / WAVE) / QT;
+    const int qi = t * 16 + (l & 15);
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (qi < Bg)
+      v = *reinterpret_cast<const u32x4_t*>(
+          q + (long)qi * D + idx_kbase(s, l >> 4, F16 ? 0 : NU));
+    *reinterpret_cast<u32x4_t*>(qfrag + (long)i * 16) = v;
+  }
+  if (tid < QT * 16) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+  }
+  if (tid < 4) live[tid] = 0;
+  __syncthreads();
+
+  const char* qf = qfrag + lane * 16;
+  const long nchunks = (N + IDX_CHUNK - 1) / IDX_CHUNK;
+  const long W = nchunks * 4;
+  const long first = blockIdx.x, grid = gridDim.x;
+  // this wave's 16 bits of a chunk: word w >> 1, upper or lower half
+  const int mword = w >> 1, mshift = (w & 1) * 16;
+  // (the lambdas must inline: a call would put acc and the captures in
+  // scratch)
+  auto row_ptr = [&](long chunk) __attribute__((always_inline)) {
+    long row = chunk * IDX_CHUNK + w * 16 + c;
+    if (row > N - 1) row = N - 1;              // its bit is clear
+    return reinterpret_cast<const char*>(rows + row * (long)D) + g * 16;
+  };
+  // does any query of the block allow a row of this wave's tile?  Lanes past
+  // the staged queries read query 0 again
+  auto tile_live = [&](int slot) __attribute__((always_inline)) {
+    const unsigned wd = mw[slot * MWS + (lane < MQ ? lane : 0) * 4 + mword];
+    return __ballot(((wd >> mshift) & 0xffffu) != 0u) != 0ull;
+  };
+  auto stage_load = [&](long chunk) __attribute__((always_inline)) {
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (tid < MQ) v = idx_mask_group(allow + (long)tid * W, chunk, N);
+    return v;
+  };
+  auto stage_store = [&](int slot, u32x4_t v) __attribute__((always_inline)) {
+    if (tid < MQ) *reinterpret_cast<u32x4_t*>(mw + slot * MWS + tid * 4) = v;
+  };
+  // scale and append the allowed rows, publish the staged words, then
+  // compact what the next chunk could overflow
+  auto finish = [&](long chunk, int slot, bool on, const f32x4 (&acc)[QT],
+                    bool stage, int sslot, u32x4_t sv)
+                    __attribute__((always_inline)) {
+    if (on) {
+      const long row = chunk * IDX_CHUNK + w * 16 + c;
+      float sc = 1.f;
+      if constexpr (!F16) sc = scales[row < N ? row : N - 1];
+      const unsigned* mq = mw + slot * MWS + mword;
+#pragma unroll
+      for (int t = 0; t < QT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qi = t * 16 + g * 4 + r;
+          const float s = F16 ? acc[t][r] : acc[t][r] * sc;
+          const unsigned bit = (mq[(MQ == 1 ? 0 : qi) * 4] >> (mshift + c)) & 1u;
+          if (qi < Bg && bit && s >= thr[qi]) {
+            const int pos = atomicAdd(&cnt[qi], 1);
+            if (pos < IDX_CAP) {
+              cand_s[qi * IDX_CAP + pos] = s;
+              cand_r[qi * IDX_CAP + pos] = (int)row;
+            }
+          }
+        }
+      }
+    }
+    if (stage) stage_store(sslot, sv);
+    __syncthreads();
+    for (int qi = w; qi < Bg; qi += IDX_WAVES)
+      if (cnt[qi] > IDX_CAP - IDX_CHUNK)
+        idx_compact(cand_s + qi * IDX_CAP, cand_r + qi * IDX_CAP, cnt + qi,
+                    thr + qi, k, lane);
+    __syncthreads();
+  };
+  // 16 bytes of a unit -> its MFMA steps
+  auto unit = [&](f32x4 (&acc)[QT], int u, u32x4_t raw)
+                  __attribute__((always_inline)) {
+    if constexpr (F16) {
+      idx_step16<QT>(acc, qf, u, raw);
+    } else {
+      idx_step<QT>(acc, qf, 2 * u, raw.x, raw.y);
+      idx_step<QT>(acc, qf, 2 * u + 1, raw.z, raw.w);
+    }
+  };
+
+  u32x4_t cur[NU_CT ? NU_CT : 1];
+#pragma unroll
+  for (int u = 0; u < (NU_CT ? NU_CT : 1); ++u) cur[u] = u32x4_t{0u, 0u, 0u, 0u};
+
+  int par = 0;
+  for (long it0 = 0; first + it0 * grid < nchunks; it0 += 64, par ^= 1) {
+    // the window's live map: lane = chunk, wave = queries w, w + 8, ..
+    {
+      const long ch = first + (it0 + lane) * grid;
+      unsigned any = 0u;
+      if (ch < nchunks)
+        for (int m = w; m < MQ; m += IDX_WAVES) {
+          const u32x4_t v = idx_mask_group(allow + (long)m * W, ch, N);
+          any |= v.x | v.y | v.z | v.w;
+        }
+      const unsigned long long bal = __ballot(any != 0u);
+      if (lane == 0 && bal) {
+        atomicOr(&live[par * 2], (unsigned)bal);
+        atomicOr(&live[par * 2 + 1], (unsigned)(bal >> 32));
+      }
+    }
+    __syncthreads();
+    unsigned long long lv =
+        (unsigned long long)__builtin_amdgcn_readfirstlane(live[par * 2]) |
+        ((unsigned long long)__builtin_amdgcn_readfirstlane(live[par * 2 + 1])
+         << 32);
+    if (tid < 2) live[(par ^ 1) * 2 + tid] = 0u;   // the next window's words
+    {
+      unsigned long long t = lv;                 // the first NSLOT - 1 chunks
+#pragma unroll
+      for (int s = 0; s < NSLOT - 1; ++s) {
+        if (t) {
+          const int l = __ffsll((long long)t) - 1;
+          t &= t - 1;
+          stage_store(s, stage_load(first + (it0 + l) * grid));
+        }
+      }
+    }
+    __syncthreads();
+
+    int slot = 0;
+    bool cur_on = false;
+    if constexpr (NU_CT > 0) {
+      if (lv) {
+        const int l = __ffsll((long long)lv) - 1;
+        cur_on = tile_live(0);
+        if (cur_on) {
+          const char* rp = row_ptr(first + (it0 + l) * grid);
+#pragma unroll
+          for (int u = 0; u < NU_CT; ++u)
+            cur[u] = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4_t*>(rp + u * 64));
+        }
+      }
+    }
+    while (lv) {
+      const long chunk = first + (it0 + __ffsll((long long)lv) - 1) * grid;
+      lv &= lv - 1;
+      // the live chunk whose words this iteration stages: the next one, or
+      // the one after it where the next one's are already needed here
+      unsigned long long ah = lv;
+      if (NU_CT) ah &= ah - 1;
+      const bool stage = ah != 0ull;
+      const int sslot = (slot + NSLOT - 1) % NSLOT;
+      u32x4_t sv = {0u, 0u, 0u, 0u};
+      if (stage)
+        sv = stage_load(first + (it0 + __ffsll((long long)ah) - 1) * grid);
+      f32x4 acc[QT];
+#pragma unroll
+      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+      if constexpr (NU_CT > 0) {
+        u32x4_t nxt[NU_CT];
+#pragma unroll
+        for (int u = 0; u < NU_CT; ++u) nxt[u] = cur[u];
+        bool nxt_on = false;
+        if (lv) {
+          nxt_on = tile_live((slot + 1) % NSLOT);
+          if (nxt_on) {
+            const char* rp =
+                row_ptr(first + (it0 + __ffsll((long long)lv) - 1) * grid);
+#pragma unroll
+            for (int u = 0; u < NU_CT; ++u)
+              nxt[u] = __builtin_nontemporal_load(
+                  reinterpret_cast<const u32x4_t*>(rp + u * 64));
+          }
+        }
+        if (cur_on) {
+#pragma unroll
+          for (int u = 0; u < NU_CT; ++u) unit(acc, u, cur[u]);
+        }
+        finish(chunk, slot, cur_on, acc, stage, sslot, sv);
+#pragma unroll
+        for (int u = 0; u < NU_CT; ++u) cur[u] = nxt[u];
+        cur_on = nxt_on;
+      } else {
+        const bool on = tile_live(slot);
+        if (on) {
+          const char* rb = row_ptr(chunk);
+          for (int u0 = 0; u0 < NU; u0 += 4) {
+            u32x4_t raw[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              raw[i] = u32x4_t{0u, 0u, 0u, 0u};
+              if (u0 + i < NU)
+                raw[i] = __builtin_nontemporal_load(
+                    reinterpret_cast<const u32x4_t*>(rb + (u0 + i) * 64));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (u0 + i < NU) unit(acc, u0 + i, raw[i]);
+          }
+          if constexpr (!F16) {
+            if (D & 32) {
+              const u32x2_t tl = __builtin_nontemporal_load(
+                  reinterpret_cast<const u32x2_t*>(rb - g * 16 + (NS - 1) * 32 +
+                                                   g * 8));
+              idx_step<QT>(acc, qf, NS - 1, tl.x, tl.y);
+            }
+          }
+        }
+        finish(chunk, slot, on, acc, stage, sslot, sv);
+      }
+      slot = (slot + 1) % NSLOT;
+    }
+  }
+
+  for (int qi = w; qi < Bg; qi += IDX_WAVES) {
+    float* cs = cand_s + qi * IDX_CAP;
+    int* cr = cand_r + qi * IDX_CAP;
+    const int n = idx_compact(cs, cr, cnt + qi, thr + qi, k, lane);
+    const long base = ((long)(qbase + qi) * gridDim.x + blockIdx.x) * k;
+    for (int i = lane; i < k; i += WAVE) {
+      ws_s[base + i] = i < n ? cs[i] : -INFINITY;
+      ws_r[base + i] = i < n ? cr[i] : -1;
+    }
+  }
+}
+
+template <typename ET, int QT, int NU_CT>
+static hipError_t launch_index_scan_masked(const void* q, const void* rows,
+                                           const float* scales,
+                                           const int* allow, int MQ,
+                                           float* ws_s, int* ws_r, long N,
+                                           int D, int Bg, int k, int qbase,
+                                           int blocks, hipStream_t stream) {
+  const size_t lds = (size_t)(D / 32) * QT * WAVE * 16 +
+                     (size_t)QT * 16 * (IDX_CAP * 8 + 8) +
+                     (size_t)(NU_CT ? 3 : 2) * QT * 16 * 16 + 16;
+  auto kern = index_scan_masked_kernel<ET, QT, NU_CT>;
+  hipError_t e = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(kern),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(IDX_WAVES * WAVE), lds,
+                     stream, (const ET*)rows, scales, (const _Float16*)q,
+                     (const unsigned*)allow, MQ, ws_s, ws_r, N, D, Bg, k,
+                     qbase);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
 extern "C" {
 
 hipError_t sentio_cosine_topk_fp8_plan(long N, int* blocks, int* chunk_rows,
@@ -689,6 +1028,47 @@ hipError_t sentio_cosine_topk_fp8(const void* q, const void* codes,
                                             D, Bg, k, b0, blocks, stream)
                   : launch_index_scan<1, 0>(qg, codes, scales, ws_s, ws_r, N,
                                             D, Bg, k, b0, blocks, stream);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)B),
+                     dim3(IDX_MERGE_THREADS), 0, stream, ws_s, ws_r, out_s,
+                     out_r, blocks * k, k);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_cosine_topk_masked(const void* q, const void* rows,
+                                     const float* scales, const int* allow,
+                                     int mask_rows, float* ws_s, int* ws_r,
+                                     float* out_s, long* out_r, long N, int D,
+                                     int B, int k, int blocks,
+                                     hipStream_t stream) {
+  if (N < 1 || N > 0x7fffffffL || D < 32 || D > 1024 || D % 32 || B < 1 ||
+      k < 1 || k > IDX_KMAX || blocks < 1 || blocks > IDX_MAX_BLOCKS ||
+      (mask_rows != 1 && mask_rows != B) || allow == nullptr ||
+      reinterpret_cast<uintptr_t>(allow) % 16)
+    return hipErrorInvalidValue;
+  const long W = 4 * ((N + IDX_CHUNK - 1) / IDX_CHUNK);
+  for (int b0 = 0; b0 < B; b0 += 32) {
+    const int Bg = B - b0 < 32 ? B - b0 : 32;
+    const void* qg = (const char*)q + (size_t)b0 * D * 2;
+    const int* ag = mask_rows == 1 ? allow : allow + (long)b0 * W;
+    const int MQ = mask_rows == 1 ? 1 : Bg;
+#define IDX_MASKED(ET, NU)                                                   \
+  (Bg > 16 ? launch_index_scan_masked<ET, 2, NU>(qg, rows, scales, ag, MQ,   \
+                                                 ws_s, ws_r, N, D, Bg, k,    \
+                                                 b0, blocks, stream)         \
+           : launch_index_scan_masked<ET, 1, NU>(qg, rows, scales, ag, MQ,   \
+                                                 ws_s, ws_r, N, D, Bg, k,    \
+                                                 b0, blocks, stream))
+    hipError_t e;
+    if (scales == nullptr)
+      e = IDX_MASKED(_Float16, 0);
+    else if (D == 1024)
+      e = IDX_MASKED(unsigned char, 16);
+    else
+      e = IDX_MASKED(unsigned char, 0);
+#undef IDX_MASKED
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)B),

@@ -140,6 +140,20 @@ hipError_t sentio_cosine_topk_fp8(const void* q, const void* codes,
                                   float* out_s, long* out_r, long N, int D,
                                   int B, int k, int blocks,
                                   hipStream_t stream);
+// the same search over the rows that a bit mask allows.  rows: e4m3fn codes
+// [N, D] with scales fp32 [N], or fp16 [N, D] when scales is null.  allow
+// int32 [mask_rows, W], mask_rows 1 (one mask for every query) or B, W = 4 *
+// ceil(N / 128); row n is bit n & 31 of word n >> 5; bits at or past N are
+// ignored.  Out as above, (-inf, -1) past the number of allowed rows.  The
+// plan, the workspace and the conditions are those of sentio_cosine_topk_fp8;
+// also hipErrorInvalidValue unless mask_rows is 1 or B and allow is 16-byte
+// aligned
+hipError_t sentio_cosine_topk_masked(const void* q, const void* rows,
+                                     const float* scales, const int* allow,
+                                     int mask_rows, float* ws_s, int* ws_r,
+                                     float* out_s, long* out_r, long N, int D,
+                                     int B, int k, int blocks,
+                                     hipStream_t stream);
 hipError_t sentio_bm25(const long* term_ids, const long* qoff,
                        const long* starts, const int* post_doc,
                        const float* post_tf, const float* idf,

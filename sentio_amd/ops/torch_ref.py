@@ -208,6 +208,54 @@ def cosine_topk_fp8(
     return vals, rows
 
 
+def pack_row_mask(allowed: torch.Tensor) -> torch.Tensor:
+    """bool [..., N] -> int32 [..., W], W = 4 * ceil(N / 128): row n is bit
+    n & 31 of word n >> 5 (the layout ops.cosine_topk_masked reads)."""
+    n = allowed.shape[-1]
+    w = 4 * ((n + 127) // 128)
+    bits = torch.zeros(*allowed.shape[:-1], w * 32, dtype=torch.int64,
+                       device=allowed.device)
+    bits[..., :n] = allowed.to(torch.int64)
+    weights = torch.ones(32, dtype=torch.int64, device=allowed.device) \
+        << torch.arange(32, device=allowed.device)
+    words = (bits.view(*allowed.shape[:-1], w, 32) * weights).sum(-1)
+    # two's complement: bit 31 makes the int32 word negative
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def unpack_row_mask(allow: torch.Tensor, n: int) -> torch.Tensor:
+    """int32 [..., W] -> bool [..., n]; bits at or past n are dropped."""
+    shifts = torch.arange(32, device=allow.device)
+    bits = (allow.to(torch.int64).unsqueeze(-1) >> shifts) & 1
+    return bits.flatten(-2)[..., :n].bool()
+
+
+def cosine_topk_masked(
+    q: torch.Tensor, rows: torch.Tensor, scales: torch.Tensor | None, k: int,
+    allow: torch.Tensor,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The filtered search's spec.  rows: e4m3fn codes with scales (scores
+    as cosine_topk_fp8) or, with scales None, plain rows (q.float() @
+    rows.float().T).  allow int32 [1 or B, W] as pack_row_mask writes it.
+    Top-k over the allowed rows by score descending, ties to the lower row,
+    padded with (-inf, -1) past the number of allowed rows."""
+    B, N = q.shape[0], rows.shape[0]
+    if scales is None:
+        scores = q.float() @ rows.float().T
+    else:
+        scores = (q.float() @ rows.view(torch.float8_e4m3fn).float().T) \
+            * scales.float()
+    ok = unpack_row_mask(allow, N).expand(B, N)
+    scores = scores.masked_fill(~ok, float("-inf"))
+    order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+    if k > N:
+        order = torch.cat([order, order.new_zeros(B, k - N)], 1)
+    idx = order[:, :k]
+    pad = torch.arange(k, device=q.device) >= ok.sum(1, keepdim=True)
+    vals = torch.gather(scores, 1, idx).masked_fill(pad, float("-inf"))
+    return vals, idx.masked_fill(pad, -1)
+
+
 def bm25_score(
     term_ids: torch.Tensor,
     indptr: torch.Tensor,

@@ -22,9 +22,12 @@ class DenseRetriever(BaseRetriever):
         self.embedder = embedder
         self.index = index
 
-    def retrieve(self, query: str, top_k: int = 10) -> list[Document]:
+    def retrieve(self, query: str, top_k: int = 10,
+                 metadata_filter: dict | None = None) -> list[Document]:
+        """metadata_filter: equality conditions on document metadata; exact
+        with a DENSE_FILTER=exact index, a post-filter otherwise."""
         qv = self.embedder.embed([query])
-        hits = self.index.search(qv, top_k)[0]
+        hits = self.index.search(qv, top_k, metadata_filter)[0]
         out: list[Document] = []
         for doc_id, score in hits:
             src = self.index.get_document(doc_id)

@@ -138,7 +138,8 @@ class ServiceContainer:
         return self._get("dense_index", lambda: DenseIndex(
             dim=self.settings.embedding_dim, device=self.device,
             dtype="fp8" if self.settings.dense_index_dtype == "fp8"
-            else torch.float16))
+            else torch.float16,
+            filter_mode=self.settings.dense_filter))
 
     def bm25_index(self) -> BM25Index:
         return self._get("bm25_index", lambda: BM25Index(
