@@ -105,6 +105,7 @@ class Settings:
     kv_cache_dtype: str = "bf16"            # bf16 | fp8 (e4m3fn session KV cache)
     dense_index_dtype: str = "fp16"         # fp16 | fp8 (e4m3fn codes + a scale per row)
     dense_filter: str = "post"              # post | exact (masked scan: exact filtered dense search)
+    bm25_search: str = "scores"             # scores | fused (batched BM25 scoring with the top-k in the kernel)
     spec_decode_tokens: int = 0             # prompt-lookup draft tokens per decode step (0: off)
     max_batch_size: int = 64          # continuous-batching slots (64 rows of KV ~ 68 GB at 8k ctx)
     dynamic_batching: bool = True           # batch concurrent /chat generations
@@ -163,6 +164,7 @@ class Settings:
         "kv_cache_dtype": "KV_CACHE_DTYPE",
         "dense_index_dtype": "DENSE_INDEX_DTYPE",
         "dense_filter": "DENSE_FILTER",
+        "bm25_search": "BM25_SEARCH",
         "spec_decode_tokens": "SPEC_DECODE_TOKENS",
         "max_batch_size": "MAX_BATCH_SIZE",
         "dynamic_batching": "DYNAMIC_BATCHING",
@@ -204,6 +206,9 @@ class Settings:
         if s.dense_filter not in ("post", "exact"):
             raise ValueError("DENSE_FILTER must be post or exact, got "
                              f"{s.dense_filter!r}")
+        if s.bm25_search not in ("scores", "fused"):
+            raise ValueError("BM25_SEARCH must be scores or fused, got "
+                             f"{s.bm25_search!r}")
         if not 0 <= s.spec_decode_tokens <= 7:
             raise ValueError("SPEC_DECODE_TOKENS must be in [0, 7], got "
                              f"{s.spec_decode_tokens}")

@@ -34,6 +34,11 @@ class BM25Index:
     b: float = 0.75
     delta: float = 1.0           # BM25+ delta
     variant: str = "okapi"       # okapi | plus
+    # scores: one ops.bm25_score launch per query, then torch.topk.
+    # fused: on a GPU, search / search_rows / search_batch go through
+    # ops.bm25_topk (batched, deterministic, no score array); shapes outside
+    # the kernel's limits and the CPU take the scores path.
+    search_mode: str = "scores"
 
     # corpus state
     doc_ids: list[str] = field(default_factory=list)
@@ -82,6 +87,10 @@ class BM25Index:
         post_doc = np.zeros(nnz, np.int32)
         post_tf = np.zeros(nnz, np.float32)
         cursor = indptr[:-1].copy()
+        # INVARIANT (ops.bm25_topk relies on it): documents are visited in
+        # ascending order, so each term's postings are sorted by document,
+        # and counts holds a term once, so a document occurs at most once in
+        # a term's list.
         for d, counts in enumerate(per_doc_counts):
             for tid, tf in counts.items():
                 p = cursor[tid]
@@ -159,6 +168,13 @@ class BM25Index:
 
     def search(self, query: str, top_k: int, device: str = "cpu") -> list[tuple[str, float]]:
         """Top-k (doc_id, score), score>0 only (reference sparse.py:183)."""
+        if device != "cpu" and self.search_mode == "fused":
+            if self.n_docs == 0:
+                return []
+            vals, rows = self.search_batch([query], top_k, device)
+            return [(self.doc_ids[i], float(v)) for i, v in
+                    zip(rows[0].cpu().tolist(), vals[0].cpu().tolist())
+                    if i >= 0]
         if device != "cpu":
             return self._search_device(query, top_k, device)
         scores = self.get_scores(query)
@@ -211,6 +227,9 @@ class BM25Index:
         if self.n_docs == 0:
             return (torch.full((top_k,), float("-inf"), device=device),
                     torch.full((top_k,), -1, dtype=torch.int64, device=device))
+        if device != "cpu" and self.search_mode == "fused":
+            vals, idx = self.search_batch([query], top_k, device)
+            return vals[0], idx[0]
         if device != "cpu":
             from sentio_amd import ops
 
@@ -237,6 +256,74 @@ class BM25Index:
             idx = torch.cat([idx, torch.full((top_k - k,), -1,
                                              dtype=torch.int64,
                                              device=idx.device)])
+        return vals, idx
+
+    def search_batch(self, queries: list[str], top_k: int,
+                     device: str = "cpu", allow=None):
+        """Batched tensor-only top-k: (scores [B, top_k] f32, rows [B, top_k]
+        i64) on `device`, score > 0 only, padded with (-inf, -1).  allow:
+        int32 [1 or B, W] row mask on `device` (ops.pack_row_mask): only
+        allowed documents are returned.  No host sync on the GPU paths.
+        search_mode "fused" on a GPU is one ops.bm25_topk call per 32
+        queries, sorted by (score desc, row asc); top_k > 128 or more than
+        1024 terms in 32 queries take the scores path (a launch and a dense
+        score vector per query, torch.topk's tie order).  The CPU path is
+        torch_ref.bm25_topk."""
+        import torch
+
+        from sentio_amd import ops
+        from sentio_amd.ops import torch_ref
+
+        B, n = len(queries), self.n_docs
+        if n == 0 or B == 0:
+            return (torch.full((B, top_k), float("-inf"), device=device),
+                    torch.full((B, top_k), -1, dtype=torch.int64,
+                               device=device))
+        if allow is not None and (
+                allow.dtype != torch.int32 or allow.dim() != 2
+                or allow.shape[0] not in (1, B)
+                or allow.shape[1] != 4 * ((n + 127) // 128)):
+            raise ValueError(f"allow must be int32 [1 or {B}, "
+                             f"{4 * ((n + 127) // 128)}]")
+        tid_lists = [self.query_term_ids(q) for q in queries]
+        qoff = torch.tensor(np.cumsum([0] + [len(t) for t in tid_lists]),
+                            dtype=torch.int32)
+        kw = dict(n_docs=n, k1=self.k1, b=self.b, avgdl=max(self.avgdl, 1e-9),
+                  plus_delta=self.delta if self.variant == "plus" else 0.0)
+        if device == "cpu":
+            a = {k: torch.from_numpy(getattr(self, k)) for k in
+                 ("indptr", "post_doc", "post_tf", "idf", "doc_len")}
+            return torch_ref.bm25_topk(
+                torch.from_numpy(np.concatenate(tid_lists).astype(np.int64)),
+                qoff, a["indptr"], a["post_doc"], a["post_tf"], a["idf"],
+                a["doc_len"], k=top_k, allow=allow, **kw)
+        if not self._device_arrays:
+            self.to_device(device)
+        a = self._device_arrays
+        if self.search_mode == "fused" and top_k <= 128 \
+                and ops.bm25_topk_fits(qoff):
+            tids = torch.from_numpy(
+                np.concatenate(tid_lists).astype(np.int64)).to(device)
+            return ops.bm25_topk(
+                tids, qoff, a["indptr"], a["post_doc"], a["post_tf"],
+                a["idf"], a["doc_len"], k=top_k,
+                allow=None if allow is None else allow.contiguous(), **kw)
+        scores = torch.stack([ops.bm25_score(
+            torch.from_numpy(t).to(device), a["indptr"], a["post_doc"],
+            a["post_tf"], a["idf"], a["doc_len"], **kw) for t in tid_lists])
+        if allow is not None:
+            scores = scores.masked_fill(
+                ~torch_ref.unpack_row_mask(allow, n).expand(B, n),
+                float("-inf"))
+        k = min(top_k, n)
+        vals, idx = torch.topk(scores, k, dim=1)
+        dead = vals <= 0.0
+        vals = vals.masked_fill(dead, float("-inf"))
+        idx = idx.masked_fill(dead, -1)
+        if k < top_k:
+            vals = torch.cat([vals, vals.new_full((B, top_k - k),
+                                                  float("-inf"))], 1)
+            idx = torch.cat([idx, idx.new_full((B, top_k - k), -1)], 1)
         return vals, idx
 
     # ----- persistence (reference sparse.py:102-157) -----

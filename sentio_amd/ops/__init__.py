@@ -664,6 +664,105 @@ def bm25_score(term_ids, indptr, post_doc, post_tf, idf, doc_len, *,
     )
 
 
+BM25_TOPK_MAX_B = 32         # queries per launch (the wrapper splits)
+BM25_TOPK_MAX_TERMS = 1024   # query terms per launch, summed over its queries
+
+
+def bm25_topk_plan(n_docs: int) -> tuple[int, int, int]:
+    """(blocks, documents per tile, candidate places per query) of
+    ops.bm25_topk over n_docs documents on the current GPU."""
+    return tuple(_require_hip().bm25_topk_plan(int(n_docs)))
+
+
+def bm25_topk_fits(qoff) -> bool:
+    """Whether every launch of 32 queries of this qoff stays within the
+    kernel's cap on query terms."""
+    off = qoff.tolist() if isinstance(qoff, torch.Tensor) else list(qoff)
+    B = len(off) - 1
+    return all(off[min(b0 + BM25_TOPK_MAX_B, B)] - off[b0]
+               <= BM25_TOPK_MAX_TERMS for b0 in range(0, B, BM25_TOPK_MAX_B))
+
+
+def bm25_topk(tids, qoff, indptr, post_doc, post_tf, idf, doc_len, *,
+              n_docs: int, k: int, k1: float, b: float, avgdl: float,
+              plus_delta: float = 0.0, allow=None):
+    """Batched BM25 search with the top-k fused into the scoring kernel: no
+    [B, N] or [N] score array.  Query i has the term ids
+    tids[qoff[i]:qoff[i+1]]: tids int64 [TT] on the index device, qoff int32
+    [B+1] (host metadata: a CPU tensor costs no sync, a GPU one is read
+    back).  CSR index on one device: indptr int64 [T+1], post_doc int32 and
+    post_tf fp32 [nnz] with each term's postings sorted by document and a
+    document at most once per term, idf fp32 [T], doc_len fp32 [n_docs].
+    allow: None, or the int32 [1 or B, W] row mask of cosine_topk_masked
+    (pack_row_mask), 16-byte aligned.  1 <= k <= 128, n_docs < 2^31, at most
+    1024 terms per 32 queries; any B (launches of 32).  Returns (scores f32
+    [B, k], rows i64 [B, k]): the allowed documents with score > 0 by score
+    descending, ties to the lower row, padded with (-inf, -1); the same
+    inputs give the same bits (torch_ref.bm25_topk is the spec and the CPU
+    path).  Nothing is converted or copied: a bad shape, dtype, device,
+    alignment or k raises ValueError before a launch."""
+    args = [("tids", tids, torch.int64, 1), ("qoff", qoff, torch.int32, 1),
+            ("indptr", indptr, torch.int64, 1),
+            ("post_doc", post_doc, torch.int32, 1),
+            ("post_tf", post_tf, torch.float32, 1),
+            ("idf", idf, torch.float32, 1),
+            ("doc_len", doc_len, torch.float32, 1)]
+    if allow is not None:
+        args.append(("allow", allow, torch.int32, 2))
+    for name, t, dt, nd in args:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd \
+                or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} {nd}-d tensor")
+        if name != "qoff" and t.device != doc_len.device:
+            raise ValueError(f"{name} is on {t.device}, doc_len on "
+                             f"{doc_len.device}")
+    N, B = int(n_docs), qoff.numel() - 1
+    if N < 1 or N >= 2 ** 31 or doc_len.numel() != N:
+        raise ValueError(f"n_docs {N} must be in [1, 2^31) and doc_len's size")
+    if indptr.numel() != idf.numel() + 1 or post_doc.numel() != post_tf.numel():
+        raise ValueError("indptr, idf, post_doc and post_tf do not agree")
+    off = qoff.tolist()
+    if B < 1 or off[0] != 0 or off[-1] != tids.numel() or \
+            any(a > z for a, z in zip(off, off[1:])):
+        raise ValueError("qoff must rise from 0 to len(tids) over B >= 1 "
+                         "queries")
+    k = int(k)
+    if not 1 <= k <= _FP8_INDEX_KMAX:
+        raise ValueError(f"k must be in [1, {_FP8_INDEX_KMAX}], got {k}")
+    if not avgdl > 0.0:
+        raise ValueError(f"avgdl must be positive, got {avgdl}")
+    if allow is not None:
+        W = 4 * ((N + 127) // 128)
+        if allow.shape[0] not in (1, B) or allow.shape[1] != W:
+            raise ValueError(f"allow must be [1 or {B}, {W}], got "
+                             f"{tuple(allow.shape)}")
+        if allow.data_ptr() % 16:
+            raise ValueError("allow must be 16-byte aligned")
+    kw = dict(k1=float(k1), b=float(b), avgdl=float(avgdl),
+              plus_delta=float(plus_delta))
+    if not _on_gpu(doc_len):
+        return torch_ref.bm25_topk(tids, qoff.cpu(), indptr, post_doc, post_tf,
+                                   idf, doc_len, n_docs=N, k=k, allow=allow,
+                                   **kw)
+    if not bm25_topk_fits(off):
+        raise ValueError(f"more than {BM25_TOPK_MAX_TERMS} query terms in a "
+                         f"launch of {BM25_TOPK_MAX_B} queries")
+    hip = _require_hip()
+    out = []
+    for b0 in range(0, B, BM25_TOPK_MAX_B):
+        b1 = min(b0 + BM25_TOPK_MAX_B, B)
+        qo = torch.tensor([o - off[b0] for o in off[b0:b1 + 1]],
+                          dtype=torch.int32).to(doc_len.device,
+                                                non_blocking=True)
+        ag = allow if allow is None or allow.shape[0] == 1 else allow[b0:b1]
+        out.append(hip.bm25_topk(tids[off[b0]:off[b1]], qo, indptr, post_doc,
+                                 post_tf, idf, doc_len, ag, k, kw["k1"],
+                                 kw["b"], kw["avgdl"], kw["plus_delta"]))
+    if len(out) == 1:
+        return out[0][0], out[0][1]
+    return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+
 # ---------------- sampling / GEMM ----------------
 
 _FUSE_METHODS = {"rrf": 0, "weighted_rrf": 1, "comb_sum": 2}

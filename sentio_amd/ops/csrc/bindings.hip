@@ -631,6 +631,65 @@ torch::Tensor bm25_score(torch::Tensor term_ids, torch::Tensor indptr,
   return scores;
 }
 
+// (blocks, documents per tile, candidate places per query) for N documents
+std::tuple<int, int, int> bm25_topk_plan(long N) {
+  int blocks = 0, tile = 0, cap = 0;
+  check_hip(sentio_bm25_topk_plan(N, &blocks, &tile, &cap), "bm25_topk_plan");
+  return {blocks, tile, cap};
+}
+
+// One launch (B <= 32) of the fused BM25 scoring + top-k; the Python wrapper
+// has checked the arguments and split the batch.  No host sync.
+std::vector<torch::Tensor> bm25_topk(
+    torch::Tensor tids, torch::Tensor qoff, torch::Tensor indptr,
+    torch::Tensor post_doc, torch::Tensor post_tf, torch::Tensor idf,
+    torch::Tensor doc_len, c10::optional<torch::Tensor> allow, int64_t k,
+    double k1, double b, double avgdl, double plus_delta) {
+  const std::pair<const torch::Tensor*, torch::ScalarType> args[] = {
+      {&tids, torch::kLong},    {&qoff, torch::kInt},
+      {&indptr, torch::kLong},  {&post_doc, torch::kInt},
+      {&post_tf, torch::kFloat}, {&idf, torch::kFloat},
+      {&doc_len, torch::kFloat}};
+  for (const auto& a : args)
+    TORCH_CHECK(a.first->is_cuda() && a.first->scalar_type() == a.second &&
+                a.first->dim() == 1 && a.first->is_contiguous(),
+                "bm25_topk: arrays must be contiguous 1-d GPU tensors of "
+                "their dtypes");
+  const long N = doc_len.size(0), B = qoff.size(0) - 1, TT = tids.size(0);
+  const long n_terms = idf.size(0);
+  TORCH_CHECK(N >= 1 && B >= 1 && k >= 1, "bm25_topk: empty input");
+  TORCH_CHECK(indptr.size(0) == n_terms + 1 &&
+              post_doc.size(0) == post_tf.size(0),
+              "bm25_topk: CSR arrays do not agree");
+  if (allow.has_value())
+    TORCH_CHECK(allow->is_cuda() && allow->scalar_type() == torch::kInt &&
+                allow->dim() == 2 && allow->is_contiguous() &&
+                (allow->size(0) == 1 || allow->size(0) == B) &&
+                allow->size(1) == 4 * ((N + 127) / 128) &&
+                reinterpret_cast<uintptr_t>(allow->data_ptr()) % 16 == 0,
+                "allow must be contiguous 16-byte aligned int32 [1 or B, 4 * "
+                "ceil(N / 128)]");
+  const int blocks = std::get<0>(bm25_topk_plan(N));
+  auto f32 = doc_len.options();
+  auto ws_s = torch::empty({B, blocks, k}, f32);
+  auto ws_r = torch::empty({B, blocks, k}, f32.dtype(torch::kInt));
+  auto out_s = torch::empty({B, k}, f32);
+  auto out_r = torch::empty({B, k}, f32.dtype(torch::kLong));
+  check_hip(sentio_bm25_topk(
+                (const long*)tids.data_ptr<int64_t>(), qoff.data_ptr<int>(),
+                (const long*)indptr.data_ptr<int64_t>(),
+                post_doc.data_ptr<int>(), post_tf.data_ptr<float>(),
+                idf.data_ptr<float>(), doc_len.data_ptr<float>(),
+                allow.has_value() ? allow->data_ptr<int>() : nullptr,
+                allow.has_value() ? (int)allow->size(0) : 1,
+                ws_s.data_ptr<float>(), ws_r.data_ptr<int>(),
+                out_s.data_ptr<float>(), (long*)out_r.data_ptr<int64_t>(), N,
+                n_terms, (int)B, (int)TT, (int)k, blocks, (float)k1, (float)b,
+                (float)avgdl, (float)plus_delta, stream()),
+            "bm25_topk");
+  return {out_s, out_r};
+}
+
 torch::Tensor flash_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                          bool causal, double scale, torch::Tensor kv_lens) {
   check_bf16_cuda(q, "q");
@@ -1091,6 +1150,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk_fp8_plan", &cosine_topk_fp8_plan);
   m.def("cosine_topk_masked", &cosine_topk_masked);
   m.def("bm25_score", &bm25_score);
+  m.def("bm25_topk", &bm25_topk);
+  m.def("bm25_topk_plan", &bm25_topk_plan);
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_cache", &flash_attn_cache);
   m.def("decode_attn", &decode_attn);

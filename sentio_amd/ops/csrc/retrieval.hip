@@ -987,7 +987,270 @@ static hipError_t launch_index_scan_masked(const void* q, const void* rows,
   return hipSuccess;
 }
 
+// --------------------------------- BM25: tiled scoring with fused top-k
+// bm25_topk_kernel scores a batch of queries against the CSR postings and
+// selects inside the scan: no [B, N] or [N] score array exists in global
+// memory.  It rests on two invariants of the index (BM25Index.
+// build_tokenized): the postings of a term are sorted by document, and a
+// document occurs at most once in a term's list.
+//
+// The corpus is cut into tiles of BM_TILE consecutive documents; a
+// persistent grid (one 8-wave block per CU, at most IDX_MAX_BLOCKS, at most
+// one per tile) walks tiles blockIdx.x + i * gridDim.x.  Per tile:
+//   1. nd[d] = k1 * (1 - b + b * doc_len[d] / avgdl) goes to LDS once for
+//      all queries.
+//   2. One lane per (query term, bound) finds by binary search on post_doc,
+//      inside [indptr[t], indptr[t+1]), the first posting at or past the
+//      tile's first document and the first past its last: every chain of
+//      dependent loads of the tile runs in this one pass.  In the same pass
+//      wave w ORs the tile's words of masks w, w + 8, ..  A query is live in
+//      the tile if one of its terms has a posting there and its mask a bit.
+//   3. Per live query the block zeroes an fp32 accumulator tile in LDS, then
+//      term by term, in query order, strides over the term's slice with a
+//      plain LDS read-add-write of idf * (tf * (k1 + 1) / (tf + nd) + delta),
+//      a block barrier after each term.  Within a term every posting is
+//      another document, so no two lanes meet: no atomics touch a score, the
+//      sum runs in query-term order, and a score is a pure function of the
+//      index and the query, whatever the tiling.  A term repeated in a query
+//      is added once per occurrence.
+//   4. Thread t owns documents 8t .. 8t+7 of the tile (one byte of a mask
+//      word: the word load serves 32 documents).  A document whose score is
+//      > 0, whose bit is set and whose score is >= the query's threshold is
+//      appended to the query's list, the lists / thresholds / idx_compact of
+//      the dense scan.  A tile can hold more candidates than a list has
+//      places (a term in every document gives BM_TILE), so an append that
+//      finds the list full stays pending: the block agrees on that with one
+//      __syncthreads_or, wave 0 compacts the list (which frees at least
+//      IDX_CAP - k places and raises the threshold) and the pending
+//      documents are tested again.  Nothing is ever written past a list and
+//      nothing that belongs to the top k is dropped.  The list is also
+//      compacted once an append passes (IDX_CAP + k) / 2, which sets the
+//      threshold early.
+// A block ends as the dense scan does, k places per query to the workspace
+// [B, blocks, k], and index_merge_kernel finishes.
+#define BM_TILE 4096                 // documents per tile (8 per thread)
+#define BM_MAX_TERMS 1024            // query terms per launch
+#define BM_THREADS (IDX_WAVES * WAVE)
+static_assert(BM_TILE == 8 * BM_THREADS, "thread t owns documents 8t .. 8t+7");
+
+__launch_bounds__(BM_THREADS)
+IDX_NO_PK_F32 __global__ void bm25_topk_kernel(
+    const long* __restrict__ tids, const int* __restrict__ qoff,
+    const long* __restrict__ indptr, const int* __restrict__ post_doc,
+    const float* __restrict__ post_tf, const float* __restrict__ idf,
+    const float* __restrict__ doc_len, const unsigned* __restrict__ allow,
+    int MQ, float* __restrict__ ws_s, int* __restrict__ ws_r, long N,
+    long n_terms, int Bg, int TT, int k, float k1, float b, float inv_avgdl,
+    float delta) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* nd = reinterpret_cast<float*>(smem);              // [BM_TILE]
+  float* acc = nd + BM_TILE;                               // [BM_TILE]
+  long* sl = reinterpret_cast<long*>(acc + BM_TILE);       // [TT][2] slice
+  float* tidf = reinterpret_cast<float*>(sl + 2 * BM_MAX_TERMS);  // [TT]
+  float* cand_s = tidf + BM_MAX_TERMS;                     // [Bg][IDX_CAP]
+  int* cand_r = reinterpret_cast<int*>(cand_s + Bg * IDX_CAP);
+  int* cnt = cand_r + Bg * IDX_CAP;                        // [32]
+  float* thr = reinterpret_cast<float*>(cnt + 32);         // [32]
+  int* qo = reinterpret_cast<int*>(thr + 32);              // [33]
+  int* mlive = qo + 33;                                    // [32] per mask
+  int* qlive = mlive + 32;                                 // [32] per query
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int w = tid / WAVE;
+  const long W = 4 * ((N + IDX_CHUNK - 1) / IDX_CHUNK);    // words of a mask
+  const long ntiles = (N + BM_TILE - 1) / BM_TILE;
+  const float k1p1 = k1 + 1.f;
+  const int lim = (IDX_CAP + k) / 2;
+
+  // a term id outside the vocabulary has no postings and no weight
+  for (int j = tid; j < TT; j += BM_THREADS) {
+    const long t = tids[j];
+    tidf[j] = (t >= 0 && t < n_terms) ? idf[t] : 0.f;
+  }
+  if (tid < 32) {
+    cnt[tid] = 0;
+    thr[tid] = -INFINITY;
+  }
+  if (tid <= Bg) qo[tid] = qoff[tid];
+  __syncthreads();
+
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long d0 = tile * BM_TILE;
+    // 1. length norms
+#pragma unroll
+    for (int i = 0; i < BM_TILE / BM_THREADS; ++i) {
+      const int d = tid + i * BM_THREADS;
+      nd[d] = d0 + d < N
+                  ? k1 * (1.f - b + b * doc_len[d0 + d] * inv_avgdl) : 0.f;
+    }
+    // 2. slices: lane = (term, bound)
+    for (int i = tid; i < 2 * TT; i += BM_THREADS) {
+      const long t = tids[i >> 1];
+      long lo = 0, hi = 0;
+      if (t >= 0 && t < n_terms) {
+        lo = indptr[t];
+        hi = indptr[t + 1];
+      }
+      const long target = d0 + (i & 1) * BM_TILE;
+      while (lo < hi) {
+        const long mid = (lo + hi) >> 1;
+        if ((long)post_doc[mid] < target) lo = mid + 1; else hi = mid;
+      }
+      sl[i] = lo;
+    }
+    // the tile's words of each mask: 128 words, two per lane
+    if (allow == nullptr) {
+      if (tid == 0) mlive[0] = 1;
+    } else {
+      for (int m = w; m < MQ; m += IDX_WAVES) {
+        const long w0 = tile * (BM_TILE / 32) + lane;
+        unsigned any = 0u;
+        if (w0 < W) any |= allow[(long)m * W + w0];
+        if (w0 + WAVE < W) any |= allow[(long)m * W + w0 + WAVE];
+        const unsigned long long bal = __ballot(any != 0u);
+        if (lane == 0) mlive[m] = bal != 0ull;
+      }
+    }
+    __syncthreads();
+    if (tid < Bg) {
+      int any = 0;
+      for (int j = qo[tid]; j < qo[tid + 1]; ++j)
+        any |= sl[2 * j + 1] > sl[2 * j] ? 1 : 0;
+      qlive[tid] = any & mlive[MQ > 1 ? tid : 0];
+    }
+    __syncthreads();
+
+    for (int q = 0; q < Bg; ++q) {
+      if (!qlive[q]) continue;                   // block-uniform
+      // 3. scores of the tile for query q
+      f32x4* mine = reinterpret_cast<f32x4*>(acc) + 2 * tid;
+      mine[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      mine[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      __syncthreads();
+      for (int j = qo[q]; j < qo[q + 1]; ++j) {
+        const long hi = sl[2 * j + 1];
+        const float wj = tidf[j];
+        for (long p = sl[2 * j] + tid; p < hi; p += BM_THREADS) {
+          const unsigned d = (unsigned)((long)post_doc[p] - d0);
+          const float tf = post_tf[p];
+          if (d < BM_TILE)                       // holds for sorted postings
+            acc[d] += wj * (tf * k1p1 / (tf + nd[d]) + delta);
+        }
+        __syncthreads();
+      }
+      // 4. select: documents 8 * tid .. 8 * tid + 7, byte tid & 3 of a word
+      const f32x4 a0 = mine[0], a1 = mine[1];
+      unsigned bits = 0xffu;
+      if (allow != nullptr) {
+        const long wi = tile * (BM_TILE / 32) + (tid >> 2);
+        const unsigned word =
+            wi < W ? allow[(long)(MQ > 1 ? q : 0) * W + wi] : 0u;
+        bits = (word >> ((tid & 3) * 8)) & 0xffu;
+      }
+      // (scalars, not an array: an indexed array would live in scratch)
+      unsigned pend = 0u;
+#define BM_EACH(F) F(a0.x, 0) F(a0.y, 1) F(a0.z, 2) F(a0.w, 3) \
+                   F(a1.x, 4) F(a1.y, 5) F(a1.z, 6) F(a1.w, 7)
+#define BM_MARK(S, J) pend |= (S > 0.f && ((bits >> J) & 1u)) ? 1u << J : 0u;
+      BM_EACH(BM_MARK)
+      float* cs = cand_s + q * IDX_CAP;
+      int* cr = cand_r + q * IDX_CAP;
+      for (;;) {
+        const float th = thr[q];
+        bool crossed = false;
+        auto offer = [&](float sj, int j) __attribute__((always_inline)) {
+          if (!((pend >> j) & 1u)) return;
+          if (sj >= th) {
+            const int pos = atomicAdd(&cnt[q], 1);
+            crossed |= pos >= lim;
+            if (pos >= IDX_CAP) return;          // full: stays pending
+            cs[pos] = sj;
+            cr[pos] = (int)(d0 + 8 * tid + j);
+          }
+          pend &= ~(1u << j);
+        };
+#define BM_OFFER(S, J) offer(S, J);
+        BM_EACH(BM_OFFER)
+#undef BM_OFFER
+#undef BM_MARK
+#undef BM_EACH
+        if (!__syncthreads_or((pend != 0u || crossed) ? 1 : 0)) break;
+        if (w == 0) idx_compact(cs, cr, cnt + q, thr + q, k, lane);
+        __syncthreads();
+      }
+    }
+    __syncthreads();                             // nd, sl, qlive are reused
+  }
+
+  for (int qi = w; qi < Bg; qi += IDX_WAVES) {
+    float* cs = cand_s + qi * IDX_CAP;
+    int* cr = cand_r + qi * IDX_CAP;
+    const int n = idx_compact(cs, cr, cnt + qi, thr + qi, k, lane);
+    const long base = ((long)qi * gridDim.x + blockIdx.x) * k;
+    for (int i = lane; i < k; i += WAVE) {
+      ws_s[base + i] = i < n ? cs[i] : -INFINITY;
+      ws_r[base + i] = i < n ? cr[i] : -1;
+    }
+  }
+}
+
 extern "C" {
+
+hipError_t sentio_bm25_topk_plan(long N, int* blocks, int* tile_docs,
+                                 int* cap) {
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return e;
+  if (N < 1 || cus < 1) return hipErrorInvalidValue;
+  const long tiles = (N + BM_TILE - 1) / BM_TILE;
+  long nb = cus < IDX_MAX_BLOCKS ? cus : IDX_MAX_BLOCKS;
+  if (nb > tiles) nb = tiles;
+  *blocks = (int)nb;
+  *tile_docs = BM_TILE;
+  *cap = IDX_CAP;
+  return hipSuccess;
+}
+
+hipError_t sentio_bm25_topk(const long* tids, const int* qoff,
+                            const long* indptr, const int* post_doc,
+                            const float* post_tf, const float* idf,
+                            const float* doc_len, const int* allow,
+                            int mask_rows, float* ws_s, int* ws_r,
+                            float* out_s, long* out_r, long N, long n_terms,
+                            int B, int TT, int k, int blocks, float k1,
+                            float b, float avgdl, float delta,
+                            hipStream_t stream) {
+  if (N < 1 || N > 0x7fffffffL || B < 1 || B > SENTIO_BM25_TOPK_MAX_B ||
+      TT < 0 || TT > SENTIO_BM25_TOPK_MAX_TERMS || k < 1 || k > IDX_KMAX ||
+      blocks < 1 || blocks > IDX_MAX_BLOCKS ||
+      blocks > (N + BM_TILE - 1) / BM_TILE || n_terms < 0 || !(avgdl > 0.f) ||
+      (allow != nullptr && ((mask_rows != 1 && mask_rows != B) ||
+                            reinterpret_cast<uintptr_t>(allow) % 16)))
+    return hipErrorInvalidValue;
+  static_assert(SENTIO_BM25_TOPK_MAX_TERMS == BM_MAX_TERMS &&
+                SENTIO_BM25_TOPK_MAX_B == 32 &&
+                SENTIO_BM25_TOPK_MAX_K == IDX_KMAX, "limits of the header");
+  const size_t lds = (size_t)2 * BM_TILE * 4 + (size_t)BM_MAX_TERMS * (16 + 4) +
+                     (size_t)B * IDX_CAP * 8 + (32 + 32 + 33 + 32 + 32) * 4;
+  hipError_t e = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(bm25_topk_kernel),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(bm25_topk_kernel, dim3((unsigned)blocks),
+                     dim3(BM_THREADS), lds, stream, tids, qoff, indptr,
+                     post_doc, post_tf, idf, doc_len, (const unsigned*)allow,
+                     allow ? mask_rows : 1, ws_s, ws_r, N, n_terms, B, TT, k,
+                     k1, b, 1.f / avgdl, delta);
+  HIP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)B),
+                     dim3(IDX_MERGE_THREADS), 0, stream, ws_s, ws_r, out_s,
+                     out_r, blocks * k, k);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 hipError_t sentio_cosine_topk_fp8_plan(long N, int* blocks, int* chunk_rows,
                                        int* cap) {

@@ -160,6 +160,42 @@ hipError_t sentio_bm25(const long* term_ids, const long* qoff,
                        const float* doc_len, float* scores, int T, long total,
                        float k1, float b, float avgdl, float delta,
                        hipStream_t stream);
+// limits of one sentio_bm25_topk launch
+#define SENTIO_BM25_TOPK_MAX_B 32        // queries
+#define SENTIO_BM25_TOPK_MAX_K 128       // results per query
+#define SENTIO_BM25_TOPK_MAX_TERMS 1024  // query terms, summed over queries
+// launch plan of sentio_bm25_topk on the current device for N documents:
+// blocks (one per CU, at most 256, at most one per tile), documents per
+// tile, places per query in a block's candidate list
+hipError_t sentio_bm25_topk_plan(long N, int* blocks, int* tile_docs,
+                                 int* cap);
+// batched BM25 search with the top-k fused into the scoring: no score array
+// in global memory.  Query b has the term ids tids[qoff[b] .. qoff[b+1])
+// (int64 [TT], qoff int32 [B+1], qoff[0] == 0, qoff[B] == TT; a term given
+// twice counts twice; an id outside [0, n_terms) has no postings).  CSR
+// index: indptr int64 [n_terms+1], post_doc int32, post_tf fp32, idf fp32
+// [n_terms], doc_len fp32 [N].  INVARIANT: within [indptr[t], indptr[t+1])
+// post_doc is strictly ascending (sorted by document, a document at most
+// once per term); the kernel finds a tile's postings by binary search and
+// adds them without atomics.  score = sum over the query's terms, in query
+// order, of idf * (tf * (k1 + 1) / (tf + k1 * (1 - b + b * doc_len /
+// avgdl)) + delta).  allow: null, or the row mask of
+// sentio_cosine_topk_masked (int32 [mask_rows, W], mask_rows 1 or B, W = 4 *
+// ceil(N / 128), bits at or past N ignored, 16-byte aligned).  out_s f32 /
+// out_r i64 [B, k]: the allowed documents with score > 0, sorted by (score
+// desc, row asc), (-inf, -1) past their number; deterministic.  ws_s / ws_r
+// hold B * blocks * k places.  hipErrorInvalidValue unless 1 <= B <= 32, 0
+// <= TT <= 1024, 1 <= k <= 128, 1 <= N < 2^31, avgdl > 0 and 1 <= blocks <=
+// min(256, tiles)
+hipError_t sentio_bm25_topk(const long* tids, const int* qoff,
+                            const long* indptr, const int* post_doc,
+                            const float* post_tf, const float* idf,
+                            const float* doc_len, const int* allow,
+                            int mask_rows, float* ws_s, int* ws_r,
+                            float* out_s, long* out_r, long N, long n_terms,
+                            int B, int TT, int k, int blocks, float k1,
+                            float b, float avgdl, float delta,
+                            hipStream_t stream);
 hipError_t sentio_fuse_topk(const long* d_ids, const float* d_scores,
                             const long* s_ids, const float* s_scores,
                             long* out_ids, float* out_scores, int B, int Kd,

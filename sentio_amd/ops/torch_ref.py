@@ -283,6 +283,48 @@ def bm25_score(
     return scores
 
 
+def bm25_topk(
+    tids: torch.Tensor,
+    qoff: torch.Tensor,
+    indptr: torch.Tensor,
+    post_doc: torch.Tensor,
+    post_tf: torch.Tensor,
+    idf: torch.Tensor,
+    doc_len: torch.Tensor,
+    *,
+    n_docs: int,
+    k: int,
+    k1: float,
+    b: float,
+    avgdl: float,
+    plus_delta: float = 0.0,
+    allow: torch.Tensor | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The batched BM25 search's spec: query i has the terms
+    tids[qoff[i]:qoff[i+1]], scored as bm25_score (a repeated term counts
+    twice); the k allowed documents with score > 0 by score descending, ties
+    to the lower row, padded with (-inf, -1).  allow: None or int32 [1 or B,
+    W] as pack_row_mask writes it.  Returns (scores [B,k] fp32, rows [B,k]
+    int64)."""
+    off = qoff.tolist()
+    B = len(off) - 1
+    scores = torch.stack([
+        bm25_score(tids[off[i]:off[i + 1]], indptr, post_doc, post_tf, idf,
+                   doc_len, n_docs, k1, b, avgdl, plus_delta)
+        for i in range(B)])
+    ok = scores > 0.0
+    if allow is not None:
+        ok = ok & unpack_row_mask(allow, n_docs)
+    scores = scores.masked_fill(~ok, float("-inf"))
+    order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+    if k > n_docs:
+        order = torch.cat([order, order.new_zeros(B, k - n_docs)], 1)
+    rows = order[:, :k]
+    pad = torch.arange(k, device=scores.device) >= ok.sum(1, keepdim=True)
+    vals = torch.gather(scores, 1, rows).masked_fill(pad, float("-inf"))
+    return vals, rows.masked_fill(pad, -1)
+
+
 def sample_token(
     logits: torch.Tensor, temperature: float, generator: torch.Generator | None = None
 ) -> torch.Tensor:

@@ -89,9 +89,16 @@ class HybridRetriever(BaseRetriever):
             rrf_k=self.rrf_k, dense_weight=self.dense_weight,
             sparse_weight=self.sparse_weight)
 
-    def retrieve(self, query: str, top_k: int = 10) -> list[Document]:
+    def retrieve(self, query: str, top_k: int = 10,
+                 metadata_filter: dict | None = None) -> list[Document]:
+        """metadata_filter: equality conditions on document metadata, handed
+        to both sides (each builds the mask in its own row numbering); the
+        cache collection is not probed under a filter."""
+        # a retriever without the parameter is still served when no filter
+        # is given
+        flt = {"metadata_filter": metadata_filter} if metadata_filter else {}
         cache_docs: list[Document] = []
-        if self.cache_retriever is not None:
+        if self.cache_retriever is not None and not metadata_filter:
             try:
                 cache_docs = self.cache_retriever.retrieve(query, top_k)
             except Exception:
@@ -104,14 +111,14 @@ class HybridRetriever(BaseRetriever):
             if len(strong) >= top_k:
                 return strong[:top_k]
 
-        dense_docs = self.dense.retrieve(query, top_k) if self.dense else []
+        dense_docs = self.dense.retrieve(query, top_k, **flt) if self.dense else []
         if cache_docs:
             seen = {d.id for d in dense_docs}
             dense_docs = dense_docs + [d for d in cache_docs
                                        if d.id not in seen]
             dense_docs.sort(key=lambda d: float(d.metadata.get("score", 0.0)),
                             reverse=True)
-        sparse_docs = self.sparse.retrieve(query, top_k) if self.sparse else []
+        sparse_docs = self.sparse.retrieve(query, top_k, **flt) if self.sparse else []
 
         dense_hits = [(d.id, float(d.metadata.get("score", 0.0))) for d in dense_docs]
         sparse_hits = [(d.id, float(d.metadata.get("bm25_score", 0.0))) for d in sparse_docs]

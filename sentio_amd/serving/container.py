@@ -144,7 +144,8 @@ class ServiceContainer:
     def bm25_index(self) -> BM25Index:
         return self._get("bm25_index", lambda: BM25Index(
             k1=self.settings.bm25_k1, b=self.settings.bm25_b,
-            variant=self.settings.bm25_variant))
+            variant=self.settings.bm25_variant,
+            search_mode=self.settings.bm25_search))
 
     # --- composition ---
     def retriever(self):
@@ -239,6 +240,7 @@ class ServiceContainer:
                 os.path.join(directory, "dense.pt"), device=self.device)
             self._cache["bm25_index"] = BM25Index.load(
                 os.path.join(directory, "bm25.npz"))
+            self._cache["bm25_index"].search_mode = self.settings.bm25_search
             for k in ("retriever", "pipeline", "ingestor"):
                 self._cache.pop(k, None)
         return {"docs": len(self.dense_index())}
@@ -313,7 +315,8 @@ class ServiceContainer:
         with self._lock:
             self._cache["bm25_index"] = BM25Index(
                 k1=self.settings.bm25_k1, b=self.settings.bm25_b,
-                variant=self.settings.bm25_variant)
+                variant=self.settings.bm25_variant,
+                search_mode=self.settings.bm25_search)
             # retriever/pipeline/ingestor hold the old bm25; rebuild them
             for k in ("retriever", "pipeline", "ingestor"):
                 self._cache.pop(k, None)
