@@ -71,6 +71,9 @@ class Settings:
     gen_top_p: float = 1.0                  # nucleus mass; 1.0 = off
     gen_top_k: int = 0                      # sampling top-k; 0 = off
     gen_seed: int = -1                      # >= 0: seed of requests that set none
+    gen_repetition_penalty: float = 1.0     # (0, 10]; 1.0 = off
+    gen_frequency_penalty: float = 0.0      # [-2, 2]; 0.0 = off
+    gen_presence_penalty: float = 0.0       # [-2, 2]; 0.0 = off
 
     # --- chunking / ingest (reference settings.py:89-90) ---
     chunk_size: int = 512
@@ -146,6 +149,9 @@ class Settings:
         "gen_top_p": "GEN_TOP_P",
         "gen_top_k": "GEN_TOP_K",
         "gen_seed": "GEN_SEED",
+        "gen_repetition_penalty": "GEN_REPETITION_PENALTY",
+        "gen_frequency_penalty": "GEN_FREQUENCY_PENALTY",
+        "gen_presence_penalty": "GEN_PRESENCE_PENALTY",
         "chunk_size": "CHUNK_SIZE",
         "chunk_overlap": "CHUNK_OVERLAP",
         "api_host": "API_HOST",

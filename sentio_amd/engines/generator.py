@@ -37,6 +37,18 @@ class SamplingParams:
     seed: int | None = None
     # a Grammar or a GrammarHandle of the engine: constrained decoding
     grammar: Any = None
+    # penalties over the tokens the request has emitted; (1, 0, 0) = off
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+
+    @property
+    def penalized(self) -> bool:
+        """True when any penalty is set: the request samples through
+        ops.sample_penalized."""
+        return (float(self.repetition_penalty) != 1.0
+                or float(self.frequency_penalty) != 0.0
+                or float(self.presence_penalty) != 0.0)
 
     @property
     def filtered(self) -> bool:
@@ -483,7 +495,7 @@ class GeneratorEngine:
                 f"(tokens + 1) <= 32, got {g} * {k + 1}")
 
     def _resolve_spec(self, speculative: int | None, grammar,
-                      on_token=None) -> int:
+                      on_token=None, penalized: bool = False) -> int:
         """Draft tokens per step for one call.  An explicit speculative > 0
         the call cannot be served with raises ValueError; the engine default
         gives way to the one-token path instead."""
@@ -493,6 +505,9 @@ class GeneratorEngine:
         why = None
         if grammar is not None:
             why = "a grammar (the automaton advances token by token)"
+        elif penalized:
+            why = ("a repetition / frequency / presence penalty (a row's "
+                   "counts change with every token it emits)")
         elif self.kv_cache_dtype == "fp8":
             why = "kv_cache_dtype='fp8'"
         elif self.model.tp.enabled:
@@ -505,6 +520,30 @@ class GeneratorEngine:
         if speculative is None:
             return 0
         raise ValueError(f"speculative decoding does not combine with {why}")
+
+    def _resolve_penalties(self, repetition_penalty, frequency_penalty,
+                           presence_penalty, grammar,
+                           max_new_tokens: int) -> tuple[float, float, float]:
+        """The three penalties of one call as floats, range-checked; all
+        neutral = the call is not penalised.  ValueError, before any
+        forward, for a penalty together with a grammar, with tensor
+        parallelism or with more new tokens than the sampler's history
+        holds."""
+        pens = (float(repetition_penalty), float(frequency_penalty),
+                float(presence_penalty))
+        ops.check_penalties(*pens)
+        if pens == (1.0, 0.0, 0.0):
+            return pens
+        if grammar is not None:
+            raise ValueError("penalties do not combine with a grammar")
+        if self.model.tp.enabled:
+            raise ValueError("penalties do not combine with tensor "
+                             "parallelism")
+        if max_new_tokens > ops.PENALTY_MAX_HISTORY:
+            raise ValueError(
+                f"penalties serve max_new_tokens <= "
+                f"{ops.PENALTY_MAX_HISTORY}, got {max_new_tokens}")
+        return pens
 
     def _spec_state(self, sess, hist_rows: list[list[int]], cur: torch.Tensor,
                     max_new: int) -> dict:
@@ -776,6 +815,9 @@ class GeneratorEngine:
         seed: int | None = None,
         grammar=None,
         speculative: int | None = None,
+        repetition_penalty: float = 1.0,
+        frequency_penalty: float = 0.0,
+        presence_penalty: float = 0.0,
     ) -> list[str]:
         """Batched generation.  Returns decoded completions (prompt excluded).
 
@@ -799,6 +841,15 @@ class GeneratorEngine:
         target model's own sample at its position.  Not available with a
         grammar, the fp8 KV cache, TP or on_token: an explicit value > 0
         then raises ValueError before any forward.
+
+        repetition_penalty / frequency_penalty / presence_penalty: (1, 0, 0)
+        is off and leaves every path above as it is.  Otherwise every step
+        samples through ops.sample_penalized (ops.sample_filtered over the
+        logits rewritten from the tokens the row has EMITTED; the prompt is
+        not counted), prompt i with seed + i; temperature 0 is the argmax of
+        the penalised row, lowest index on ties.  Not available with a
+        grammar or TP (ValueError); an explicit speculative > 0 raises, the
+        engine's spec_tokens gives way to the one-token path.
         """
         if not prompts:
             return []
@@ -808,7 +859,13 @@ class GeneratorEngine:
         handle = self.resolve_grammar(grammar)
         if handle is not None:
             self.check_grammar_budget(handle, max_new_tokens)
-        spec_k = self._resolve_spec(speculative, handle, on_token)
+        pens = self._resolve_penalties(repetition_penalty, frequency_penalty,
+                                       presence_penalty, handle,
+                                       max_new_tokens)
+        params = SamplingParams(temperature, top_k, top_p, seed, handle,
+                                *pens)
+        spec_k = self._resolve_spec(speculative, handle, on_token,
+                                    params.penalized)
         import time as _time
 
         from sentio_amd.observability.kernel_timer import get_timer
@@ -818,9 +875,7 @@ class GeneratorEngine:
             with get_timer("generate").measure():
                 return self._generate_locked(
                     prompts, max_new_tokens, temperature, stop_on_eos,
-                    on_token, _time,
-                    SamplingParams(temperature, top_k, top_p, seed, handle),
-                    spec_k)
+                    on_token, _time, params, spec_k)
         finally:
             self._gen_lock.release()
 
@@ -894,7 +949,7 @@ class GeneratorEngine:
             # one base seed for the first token's sampler and the loop's
             sampling = replace(sampling, seed=self.derive_seed())
         sampler = self._make_sampler(sampling, temperature, B,
-                                     max_new_tokens)
+                                     max_new_tokens, toks_buf)
         cur = sampler(logits, 0)
         n_steps = max_new_tokens
         row_lens = None
@@ -971,16 +1026,22 @@ class GeneratorEngine:
 
     def _make_sampler(self, sampling: SamplingParams | None,
                       temperature: float, batch: int,
-                      max_new_tokens: int = 0):
+                      max_new_tokens: int = 0, out_buf=None):
         """sampler(logits, step) for one generate/stream call.  Default
         parameters: the present path (_sample -> ops.sample_token, same
         seeds, same tokens).  Otherwise ops.sample_filtered with per-row
         arrays built once; only the step counter changes per token.  With a
         grammar: ops.sample_constrained for any parameters, every row (the
         padding rows of a bucketed batch too) from the grammar's start
-        state with left = max_new_tokens."""
+        state with left = max_new_tokens.  With a penalty:
+        ops.sample_penalized, whose history is `out_buf` (int64 [batch,
+        max_new_tokens], the loop's token buffer; the kernel appends each
+        token where the loop stores it) with the row lengths and the step
+        counters on the device."""
         handle = sampling.grammar if sampling is not None else None
-        if handle is None and (sampling is None or not sampling.filtered):
+        penalized = sampling is not None and sampling.penalized
+        if handle is None and not penalized \
+                and (sampling is None or not sampling.filtered):
             return lambda logits, _step: self._sample(logits, temperature)
         dev = self.device
         base = sampling.seed if sampling.seed is not None \
@@ -1006,6 +1067,27 @@ class GeneratorEngine:
 
             return constrained
 
+        if penalized:
+            if out_buf is None:
+                out_buf = torch.zeros(batch, max(1, max_new_tokens),
+                                      dtype=torch.int64, device=dev)
+            out_len = torch.zeros(batch, dtype=torch.int32, device=dev)
+            steps = torch.zeros(batch, dtype=torch.int32, device=dev)
+            # range-checked by _resolve_penalties; on the device once, so
+            # the per-step call neither uploads nor reads anything back
+            rep, freq, pres = (
+                torch.full((batch,), float(v), device=dev)
+                for v in (sampling.repetition_penalty,
+                          sampling.frequency_penalty,
+                          sampling.presence_penalty))
+
+            def penalized_sampler(logits, _step):
+                return ops.sample_penalized(logits, temps, ks, ps, seeds,
+                                            steps, out_buf, out_len, rep,
+                                            freq, pres)
+
+            return penalized_sampler
+
         def sampler(logits, step):
             steps = torch.full((batch,), int(step), dtype=torch.int32,
                                device=dev)
@@ -1017,7 +1099,10 @@ class GeneratorEngine:
     def stream(self, prompt: str, max_new_tokens: int = 128,
                temperature: float = 0.3, top_k: int = 0, top_p: float = 1.0,
                seed: int | None = None, grammar=None,
-               speculative: int | None = None) -> Iterator[str]:
+               speculative: int | None = None,
+               repetition_penalty: float = 1.0,
+               frequency_penalty: float = 0.0,
+               presence_penalty: float = 0.0) -> Iterator[str]:
         """Yield text deltas token-by-token (single prompt) — the on-device
         equivalent of the reference's SSE streaming (openai.py:149-157).
         Holds the generation lock for the stream's duration (the pooled
@@ -1025,22 +1110,29 @@ class GeneratorEngine:
         handle = self.resolve_grammar(grammar)
         if handle is not None:
             self.check_grammar_budget(handle, max_new_tokens)
-        spec_k = self._resolve_spec(speculative, handle)
+        pens = self._resolve_penalties(repetition_penalty, frequency_penalty,
+                                       presence_penalty, handle,
+                                       max_new_tokens)
+        spec_k = self._resolve_spec(speculative, handle,
+                                    penalized=pens != (1.0, 0.0, 0.0))
         with self._gen_lock:
             yield from self._stream_locked(prompt, max_new_tokens, temperature,
-                                           top_k, top_p, seed, handle, spec_k)
+                                           top_k, top_p, seed, handle, spec_k,
+                                           pens)
 
     def _stream_locked(self, prompt: str, max_new_tokens: int,
                        temperature: float, top_k: int = 0,
                        top_p: float = 1.0,
                        seed: int | None = None,
-                       grammar=None, spec_k: int = 0) -> Iterator[str]:
+                       grammar=None, spec_k: int = 0,
+                       pens=(1.0, 0.0, 0.0)) -> Iterator[str]:
         prompt_budget = self.max_seq - max_new_tokens - 1
         ids = self.tokenizer.encode(prompt[-4 * prompt_budget:], prompt_budget)
         tokens = torch.tensor([ids], dtype=torch.int64, device=self.device)
         sess = self._decode_session(1, self.max_seq)
         logits = sess.prefill(tokens)
-        params = SamplingParams(temperature, top_k, top_p, seed, grammar)
+        params = SamplingParams(temperature, top_k, top_p, seed, grammar,
+                                *pens)
         if max_new_tokens < 1:
             spec_k = 0      # nothing to emit: the one-token path's empty loop
         if spec_k > 0 and params.filtered and seed is None:

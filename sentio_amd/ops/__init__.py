@@ -934,6 +934,85 @@ def sample_slots(logits, slot, temperature, top_k, top_p, seed, step, active,
                            step, active, tok)
 
 
+PENALTY_MAX_HISTORY = 4096      # out_buf columns the penalised sampler serves
+PENALTY_MAX_VOCAB = 1 << 18     # exclusive
+
+
+def check_penalties(repetition_penalty=1.0, frequency_penalty=0.0,
+                    presence_penalty=0.0) -> None:
+    """ValueError unless 0 < rep <= 10 and -2 <= freq, pres <= 2 (scalars or
+    host tensors; NaN fails)."""
+    def every(v, lo_open, lo, hi):
+        t = torch.as_tensor(v, dtype=torch.float32)
+        return bool(((t > lo) if lo_open else (t >= lo)).all()
+                    and (t <= hi).all())
+
+    if not every(repetition_penalty, True, 0.0, 10.0):
+        raise ValueError("repetition_penalty must be in (0, 10], got "
+                         f"{repetition_penalty}")
+    for name, v in (("frequency_penalty", frequency_penalty),
+                    ("presence_penalty", presence_penalty)):
+        if not every(v, False, -2.0, 2.0):
+            raise ValueError(f"{name} must be in [-2, 2], got {v}")
+
+
+def sample_penalized(logits, temperature, top_k, top_p, seed, step, out_buf,
+                     out_len, repetition_penalty=1.0, frequency_penalty=0.0,
+                     presence_penalty=0.0):
+    """ops.sample_filtered over logits rewritten by repetition / frequency /
+    presence penalties (torch_ref.apply_penalties is the spec), IN PLACE on
+    `step`, `out_buf` and `out_len`, so a decode loop needs no host round
+    trip between steps.
+
+    logits [B, V] with V < 2^18; temperature / top_k / top_p / seed are [B]
+    or scalars.  step int32 [B], out_buf int64 [B, L <= 4096] and out_len
+    int32 [B] are contiguous tensors of exactly these dtypes on the logits'
+    device: out_buf[b, :out_len[b]] are the tokens row b has emitted (the
+    prompt is not counted).  The penalties are scalars or [B], range-checked
+    here before any launch: 0 < rep <= 10, -2 <= freq, pres <= 2.  Reading a
+    DEVICE tensor back would sync the decode loop, so one already on the
+    logits' device is taken as checked: its owner calls check_penalties on
+    the host values once, as the engine does.
+
+    Returns tok [B] int64; then out_buf[b, out_len[b]] = tok[b] and
+    out_len[b] += 1 while the row has room, and step[b] += 1 always.  With
+    neutral penalties (1, 0, 0) the token is ops.sample_filtered's."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 \
+            or logits.numel() == 0 or not logits.is_floating_point():
+        raise ValueError("logits must be a non-empty floating [B, V] tensor")
+    B, V = logits.shape
+    dev = logits.device
+    if V >= PENALTY_MAX_VOCAB:
+        raise ValueError(f"sample_penalized serves V < {PENALTY_MAX_VOCAB}, "
+                         f"got {V}")
+    _check_slot_array(step, "step", B, torch.int32, dev)
+    _check_slot_array(out_len, "out_len", B, torch.int32, dev)
+    if not isinstance(out_buf, torch.Tensor) or out_buf.dtype != torch.int64 \
+            or out_buf.dim() != 2 or out_buf.shape[0] != B \
+            or not out_buf.is_contiguous() or out_buf.device != dev:
+        raise ValueError(f"out_buf must be a contiguous int64 [{B}, L] "
+                         f"tensor on {dev}")
+    L = out_buf.shape[1]
+    if not 1 <= L <= PENALTY_MAX_HISTORY:
+        raise ValueError(f"out_buf must have 1 .. {PENALTY_MAX_HISTORY} "
+                         f"columns, got {L}")
+    pens = (repetition_penalty, frequency_penalty, presence_penalty)
+    neutral = (1.0, 0.0, 0.0)
+    check_penalties(*(n if isinstance(v, torch.Tensor) and v.is_cuda else v
+                      for v, n in zip(pens, neutral)))
+    t = _row_tensor(temperature, B, torch.float32, dev)
+    k = _row_tensor(top_k, B, torch.int32, dev)
+    p = _row_tensor(top_p, B, torch.float32, dev)
+    sd = _row_tensor(seed, B, torch.int64, dev)
+    rp, fq, ps = (_row_tensor(v, B, torch.float32, dev) for v in pens)
+    if _on_gpu(logits):
+        return _require_hip().sample_penalized(
+            logits.contiguous(), t, k, p, sd, step, out_buf, out_len, rp, fq,
+            ps)
+    return torch_ref.sample_penalized(logits, t, k, p, sd, step, out_buf,
+                                      out_len, rp, fq, ps)
+
+
 def ngram_draft(hist, hist_len, room, K: int, n_max: int = 3):
     """Prompt-lookup draft for speculative decoding.  hist int64 [B, L] holds
     each row's tokens, hist_len int32 [B] of them valid, room int32 [B] caps
@@ -1213,5 +1292,5 @@ def gemm_bf16(a, b):
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_verify", "ngram_draft", "spec_accept", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
     "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok", "cosine_topk_masked", "pack_row_mask",
-    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
+    "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_penalized", "check_penalties", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

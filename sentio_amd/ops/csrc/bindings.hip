@@ -495,6 +495,47 @@ void sample_slots_constrained(
       "sample_slots_constrained");
 }
 
+// In place on step, out_buf and out_len, which therefore must already have
+// their kernel dtypes; the read-only parameters are converted like
+// sample_filtered's.  Returns tok [B] int64.
+torch::Tensor sample_penalized(torch::Tensor logits, torch::Tensor temperature,
+                               torch::Tensor top_k, torch::Tensor top_p,
+                               torch::Tensor seed, torch::Tensor step,
+                               torch::Tensor out_buf, torch::Tensor out_len,
+                               torch::Tensor rep, torch::Tensor freq,
+                               torch::Tensor pres) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "logits must be [B,V] GPU");
+  auto l = logits.to(torch::kFloat).contiguous();
+  const long B = l.size(0);
+  TORCH_CHECK(B > 0 && l.size(1) > 0, "logits must be non-empty");
+  auto t = row_param(temperature, l, torch::kFloat, "temperature");
+  auto k = row_param(top_k, l, torch::kInt, "top_k");
+  auto p = row_param(top_p, l, torch::kFloat, "top_p");
+  auto sd = row_param(seed, l, torch::kLong, "seed");
+  auto rp = row_param(rep, l, torch::kFloat, "repetition_penalty");
+  auto fq = row_param(freq, l, torch::kFloat, "frequency_penalty");
+  auto ps = row_param(pres, l, torch::kFloat, "presence_penalty");
+  auto inplace = [&](const torch::Tensor& x, torch::ScalarType dt, int64_t dim,
+                     const char* name) {
+    TORCH_CHECK(x.dim() == dim && x.size(0) == B && x.scalar_type() == dt &&
+                x.is_contiguous() && x.device() == l.device(), name,
+                " must be a contiguous tensor of its kernel dtype with B rows "
+                "on the logits' device");
+  };
+  inplace(step, torch::kInt, 1, "step");
+  inplace(out_len, torch::kInt, 1, "out_len");
+  inplace(out_buf, torch::kLong, 2, "out_buf");
+  auto out = torch::empty({B}, l.options().dtype(torch::kLong));
+  check_hip(sentio_sample_penalized(
+      l.data_ptr<float>(), t.data_ptr<float>(), k.data_ptr<int>(),
+      p.data_ptr<float>(), (const long*)sd.data_ptr<int64_t>(),
+      step.data_ptr<int>(), (long*)out_buf.data_ptr<int64_t>(),
+      out_len.data_ptr<int>(), rp.data_ptr<float>(), fq.data_ptr<float>(),
+      ps.data_ptr<float>(), (long*)out.data_ptr<int64_t>(), B, (int)l.size(1),
+      (int)out_buf.size(1), stream()), "sample_penalized");
+  return out;
+}
+
 torch::Tensor cosine_scores(torch::Tensor q, torch::Tensor mat) {
   TORCH_CHECK(q.is_cuda() && mat.is_cuda(), "must be on GPU");
   TORCH_CHECK(q.scalar_type() == mat.scalar_type(), "q/mat dtype mismatch");
@@ -1141,6 +1182,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_support", &sample_support);
   m.def("sample_filtered", &sample_filtered);
   m.def("sample_slots", &sample_slots);
+  m.def("sample_penalized", &sample_penalized);
   m.def("ngram_draft", &ngram_draft);
   m.def("spec_accept", &spec_accept);
   m.def("sample_constrained", &sample_constrained);

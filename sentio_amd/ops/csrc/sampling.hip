@@ -8,6 +8,10 @@
 //   sample_slots   : sample_filtered over a slot table: row r samples with
 //                    the parameters of slot[r], skips free slots, writes the
 //                    token into tok[slot] and advances step[slot] in place.
+//   sample_penalized: sample_filtered over logits rewritten on the fly by
+//                    repetition / frequency / presence penalties from the
+//                    row's emitted tokens (a token -> count table in LDS);
+//                    appends the token to the row's history in place.
 //
 // One 1024-thread block per row; nothing is sorted.  tau is found by a radix
 // descent (4 levels x 8 bits) on an order-preserving uint32 key of the RAW
@@ -16,6 +20,11 @@
 // histogram, scans it from the top and descends into the bin where the
 // cumulative count crosses top_k (top-k) or the cumulative probability mass
 // crosses top_p * M_k (top-p, after top-k, renormalised over the survivors).
+// Every pass visits the row through a functor (SfAll, ScAllowed,
+// SpPenalised); the key is taken from the value the functor returns.  A
+// masked or penalised logit is a pure function of (raw logit, v, per-row
+// tables that no pass writes), so every pass sees the same value and tau is
+// bit-exact for the rewritten row as well.
 //
 // Probability mass is accumulated in FIXED POINT: m = exp(z - zmax) * 2^40 as
 // a 64-bit integer.  Integer adds are associative, so the histogram is
@@ -154,7 +163,7 @@ __device__ __forceinline__ u64 sf_block_sum64(u64 v, SfShared& sh) {
 // pfrac * (row total) once the level-0 histogram knows the total.
 // Returns K; above = weight strictly above K's group.
 template <bool MASS, class A = SfAll>
-__device__ unsigned sf_descend(const float* __restrict__ lb, int V, float xmax,
+__device__ __forceinline__ unsigned sf_descend(const float* __restrict__ lb, int V, float xmax,
                                float invT, u64 target, float pfrac,
                                SfShared& sh, u64& above_out,
                                const A& allow = A()) {
@@ -580,6 +589,156 @@ __global__ __launch_bounds__(SF_THREADS) void sample_constrained_kernel(
   }
 }
 
+// ---- repetition / frequency / presence penalties
+//
+// A row's emitted tokens out_buf[b, :out_len[b]] (the prompt is not counted)
+// are folded ONCE per launch into an open-addressed token -> count table in
+// LDS: 2 * 4096 one-word slots, (token << 13) | count, claimed by atomicCAS
+// and counted by atomicAdd, linear probing from a multiplicative hash.  The
+// launcher enforces L <= 4096 and V < 2^18, so a count fits 13 bits, a token
+// 18, the all-ones word is free to mean "empty" and the load factor stays
+// <= 1/2.  Beside it a 64 Kbit "seen" filter indexed by the token's low 16
+// bits: the tokens a thread and its wave neighbours visit together share
+// filter words (LDS broadcasts, no bank conflicts), and the ~99.9 % of the
+// vocabulary that was never emitted costs one LDS bit test per visit and
+// never probes the table.
+//
+// A token with count c > 0 has its cleaned logit x rewritten to
+//   x = x < 0 ? x * rep : x / rep;  x -= freq * c;  x -= pres
+// with every operation rounded to fp32 on its own (contraction is off in
+// sp_apply: a fused multiply-add would round differently from the reference
+// and tau would no longer be bit-exact).
+#define SP_MAX_HIST 4096
+#define SP_SLOTS (2 * SP_MAX_HIST)
+#define SP_CNT_BITS 13
+#define SP_EMPTY 0xffffffffu
+#define SP_SEEN_BITS 65536
+#define SP_SEEN_WORDS (SP_SEEN_BITS / 32)
+#define SP_LDS_BYTES ((SP_SLOTS + SP_SEEN_WORDS) * 4)
+#define SP_MAX_V (1 << 18)
+static_assert(SP_MAX_HIST < (1 << SP_CNT_BITS), "a count fits its field");
+static_assert(((SP_MAX_V - 1) >> (32 - SP_CNT_BITS)) == 0 &&
+              (SP_EMPTY >> SP_CNT_BITS) >= SP_MAX_V,
+              "a token fits above the count and never reads as empty");
+// fp32 VALU work stays on the scalar forms, as in verify_attn_kernel and for
+// the reason given there (attention.hip, VER_NO_PK_F32)
+#define SP_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+typedef long l64x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned sp_hash(unsigned v) {
+  return (v * 0x9E3779B1u) >> 19;  // top 13 bits: a slot in [0, SP_SLOTS)
+}
+static_assert(SP_SLOTS == 1 << 13, "sp_hash returns 13 bits");
+
+__device__ __forceinline__ float sp_apply(float x, unsigned c, float rep,
+                                          float freq, float pres) {
+#pragma clang fp contract(off)
+  x = x < 0.f ? x * rep : x / rep;
+  const float f = freq * (float)c;
+  x = x - f;
+  x = x - pres;
+  return x + 0.0f;  // -0 -> +0, as sf_clean
+}
+
+// One emitted token into the table and the filter; ids outside [0, V) are
+// ignored.  At most SP_MAX_HIST distinct tokens meet SP_SLOTS slots, so the
+// probe always ends on the token's slot or an empty one.
+__device__ __forceinline__ void sp_insert(unsigned* table, unsigned* seen,
+                                          long t, int V) {
+  if (t < 0 || t >= V) return;
+  const unsigned v = (unsigned)t;
+  atomicOr(&seen[(v & (SP_SEEN_BITS - 1)) >> 5], 1u << (v & 31));
+  unsigned h = sp_hash(v);
+  for (int i = 0; i < SP_SLOTS; ++i) {
+    const unsigned w = atomicCAS(&table[h], SP_EMPTY, v << SP_CNT_BITS);
+    if (w == SP_EMPTY || (w >> SP_CNT_BITS) == v) {
+      atomicAdd(&table[h], 1u);
+      return;
+    }
+    h = (h + 1) & (SP_SLOTS - 1);
+  }
+}
+
+// Whole block: clear, then fold hist[0 .. n) in with 16-byte loads (a row
+// of int64 starts 8-byte aligned: one scalar head / tail element).  Ends on
+// a block barrier.
+__device__ __forceinline__ void sp_build(unsigned* table, unsigned* seen,
+                                         const long* hist, int n, int V) {
+  for (int i = threadIdx.x; i < SP_SLOTS; i += SF_THREADS) table[i] = SP_EMPTY;
+  for (int i = threadIdx.x; i < SP_SEEN_WORDS; i += SF_THREADS) seen[i] = 0u;
+  __syncthreads();
+  const int head = min(n, (int)((reinterpret_cast<size_t>(hist) >> 3) & 1));
+  const int nvec = (n - head) >> 1;
+  const l64x2* vp = reinterpret_cast<const l64x2*>(hist + head);
+  for (int i = threadIdx.x; i < nvec; i += SF_THREADS) {
+    const l64x2 q = vp[i];
+    sp_insert(table, seen, q.x, V);
+    sp_insert(table, seen, q.y, V);
+  }
+  const int done = head + 2 * nvec;
+  if (threadIdx.x == 0 && head) sp_insert(table, seen, hist[0], V);
+  if (threadIdx.x == 1 && done < n) sp_insert(table, seen, hist[done], V);
+  __syncthreads();
+}
+
+struct SpPenalised {
+  const unsigned* table;
+  const unsigned* seen;
+  float rep, freq, pres;
+  __device__ __forceinline__ float operator()(float x, int v) const {
+    if (!((seen[(v & (SP_SEEN_BITS - 1)) >> 5] >> (v & 31)) & 1u)) return x;
+    unsigned h = sp_hash((unsigned)v);
+    unsigned c = 0;
+    for (int i = 0; i < SP_SLOTS; ++i) {
+      const unsigned w = table[h];
+      if (w == SP_EMPTY) break;
+      if ((w >> SP_CNT_BITS) == (unsigned)v) {
+        c = w & ((1u << SP_CNT_BITS) - 1u);
+        break;
+      }
+      h = (h + 1) & (SP_SLOTS - 1);
+    }
+    return c ? sp_apply(x, c, rep, freq, pres) : x;
+  }
+};
+
+// Row b: sample_filtered's arithmetic over the penalised row at step[b];
+// then, by thread 0, tok[b], the append out_buf[b, out_len[b]] = tok with
+// out_len[b] += 1 while the row has room (0 <= out_len[b] < L), and
+// step[b] += 1.  A row without room still samples, from its first L tokens.
+__launch_bounds__(SF_THREADS)
+SP_NO_PK_F32 __global__ void sample_penalized_kernel(
+    const float* __restrict__ logits, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const float* __restrict__ top_p,
+    const long* __restrict__ seed, int* __restrict__ step,
+    long* __restrict__ out_buf, int* __restrict__ out_len,
+    const float* __restrict__ rep, const float* __restrict__ freq,
+    const float* __restrict__ pres, long* __restrict__ tok, int V, int L) {
+  __shared__ SfShared sh;
+  extern __shared__ __attribute__((aligned(16))) unsigned sp_lds[];
+  unsigned* table = sp_lds;             // [SP_SLOTS]
+  unsigned* seen = sp_lds + SP_SLOTS;   // [SP_SEEN_WORDS]
+  const long b = blockIdx.x;
+  const int st = step[b];
+  const int ol = out_len[b];
+  long* hb = out_buf + b * (long)L;
+  sp_build(table, seen, hb, max(0, min(ol, L)), V);
+  const SpPenalised pen{table, seen, rep[b], freq[b], pres[b]};
+  const float* lb = logits + b * (long)V;
+  const SfRow r = sf_threshold(lb, V, temperature[b], top_k[b], top_p[b], sh,
+                               pen);
+  const long t = sf_gumbel_argmax(lb, V, r, seed[b], st, sh, pen);
+  if (threadIdx.x == 0) {
+    tok[b] = t;
+    if (ol >= 0 && ol < L) {
+      hb[ol] = t;
+      out_len[b] = ol + 1;
+    }
+    step[b] = st + 1;
+  }
+}
+
 // ------------------------------------------------- speculative bookkeeping
 // Prompt-lookup drafting and the accept step of speculative decoding, on the
 // device so the verify loop has no per-step host sync.  Integer work only.
@@ -775,6 +934,27 @@ hipError_t sentio_sample_slots(const float* logits, const int* slot,
   hipLaunchKernelGGL(sample_slots_kernel, dim3((unsigned)R), dim3(SF_THREADS),
                      0, stream, logits, slot, temperature, top_k, top_p, seed,
                      step, active, tok, S, V);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t sentio_sample_penalized(
+    const float* logits, const float* temperature, const int* top_k,
+    const float* top_p, const long* seed, int* step, long* out_buf,
+    int* out_len, const float* rep, const float* freq, const float* pres,
+    long* tok, long B, int V, int L, hipStream_t stream) {
+  if (B <= 0 || B > 0x7fffffffL || V <= 0 || V >= SP_MAX_V || L <= 0 ||
+      L > SP_MAX_HIST)
+    return hipErrorInvalidValue;
+  // SfShared is static; the table and the filter take the total past 64 KB
+  hipError_t e = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(sample_penalized_kernel),
+      hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_BYTES);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sample_penalized_kernel, dim3((unsigned)B),
+                     dim3(SF_THREADS), SP_LDS_BYTES, stream, logits,
+                     temperature, top_k, top_p, seed, step, out_buf, out_len,
+                     rep, freq, pres, tok, V, L);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

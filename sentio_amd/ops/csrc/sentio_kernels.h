@@ -99,6 +99,21 @@ hipError_t sentio_sample_slots_constrained(
     const unsigned char* active, long* tok, int* state, int* left,
     const short* next, const int* mask, const short* dist, long R, int S,
     int V, int Vt, int N, int W, int max_dist, hipStream_t stream);
+// sample_filtered over logits [B, V] rewritten by repetition / frequency /
+// presence penalties.  out_buf int64 [B, L] holds each row's emitted tokens,
+// out_len int32 [B] of them valid (clamped to [0, L]; ids outside [0, V)
+// are ignored); rep / freq / pres are f32 [B].  A token with count c > 0
+// samples from x = (x < 0 ? x * rep : x / rep) - freq * c - pres, each
+// operation rounded on its own.  In: logits, temperature, top_k, top_p,
+// seed, rep, freq, pres.  In/out: step (+= 1), out_buf and out_len (the
+// token is appended while 0 <= out_len[b] < L, else both are kept).  Out:
+// tok int64 [B].  Dims are (B, V, L); hipErrorInvalidValue unless
+// 1 <= B <= 2^31 - 1, 1 <= V < 2^18 and 1 <= L <= 4096
+hipError_t sentio_sample_penalized(
+    const float* logits, const float* temperature, const int* top_k,
+    const float* top_p, const long* seed, int* step, long* out_buf,
+    int* out_len, const float* rep, const float* freq, const float* pres,
+    long* tok, long B, int V, int L, hipStream_t stream);
 // prompt-lookup draft: hist int64 [B, L], hist_len / room int32 [B] ->
 // draft int64 [B, K], n_draft int32 [B]; dims are (B, L, K, n_max)
 hipError_t sentio_ngram_draft(const long* hist, const int* hist_len,

@@ -452,6 +452,69 @@ def sample_slots(logits: torch.Tensor, slot, temperature, top_k, top_p, seed,
         step[s] += 1
 
 
+def _penalty_param(v, B: int, device) -> torch.Tensor:
+    t = torch.as_tensor(v).detach().to(device=device,
+                                       dtype=torch.float32).flatten()
+    return (t.expand(B) if t.numel() == 1 else t).reshape(B, 1)
+
+
+def apply_penalties(logits: torch.Tensor, out_buf: torch.Tensor,
+                    out_len: torch.Tensor, rep, freq, pres) -> torch.Tensor:
+    """Repetition / frequency / presence penalties -> fp32 [B, V], on the
+    logits' device.
+
+    out_buf int64 [B, L] and out_len int32 [B] hold the tokens each row has
+    EMITTED so far.  The prompt is not counted: a RAG answer is supposed to
+    quote its context, so penalising prompt tokens would work against the
+    product.  rep / freq / pres are fp32 [B] (a scalar broadcasts).
+
+    For token v with count c > 0 among out_buf[b, :min(out_len[b], L)] (ids
+    outside [0, V) are ignored), starting from the cleaned logit (NaN ->
+    -inf), in this order and each operation rounded to fp32 on its own:
+        x = x * rep  if x < 0  else  x / rep
+        x = x - freq * float(c)
+        x = x - pres
+    Tokens with c == 0 are untouched."""
+    x = logits.detach().float()
+    B, V = x.shape
+    dev = x.device
+    buf = out_buf.detach().to(dev)
+    L = buf.shape[1]
+    n = out_len.detach().to(dev).to(torch.int64).clamp(0, L)
+    ok = (torch.arange(L, device=dev)[None, :] < n[:, None]) \
+        & (buf >= 0) & (buf < V)
+    cnt = torch.zeros(B, V, dtype=torch.int64, device=dev)
+    cnt.scatter_add_(1, torch.where(ok, buf, torch.zeros_like(buf)),
+                     ok.to(torch.int64))
+    r, f, p = (_penalty_param(v, B, dev) for v in (rep, freq, pres))
+    xc = torch.where(torch.isnan(x), torch.full_like(x, -math.inf), x)
+    # tensor operands throughout: every line is one fp32 operation (a Python
+    # scalar divisor may be turned into a multiplication by its reciprocal)
+    y = torch.where(xc < 0, xc * r, xc / r)
+    y = y - f * cnt.to(torch.float32)
+    y = y - p
+    return torch.where(cnt > 0, y, x)
+
+
+def sample_penalized(logits: torch.Tensor, temperature, top_k, top_p, seed,
+                     step: torch.Tensor, out_buf: torch.Tensor,
+                     out_len: torch.Tensor, rep, freq, pres) -> torch.Tensor:
+    """sample_filtered on apply_penalties(...), then the append, in place:
+    out_buf[b, out_len[b]] = tok, out_len[b] += 1, step[b] += 1.  A row with
+    out_len[b] >= L samples but appends nothing (step still advances)."""
+    tok = sample_filtered(
+        apply_penalties(logits, out_buf, out_len, rep, freq, pres),
+        temperature, top_k, top_p, seed, step)
+    L = out_buf.shape[1]
+    for b in range(tok.shape[0]):
+        n = int(out_len[b])
+        if 0 <= n < L:
+            out_buf[b, n] = tok[b]
+            out_len[b] += 1
+        step[b] += 1
+    return tok
+
+
 def constrained_allowed(state: int, left: int, V: int, nxt: torch.Tensor,
                         mask: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
     """bool [V]: the tokens a row in automaton state `state` with `left`

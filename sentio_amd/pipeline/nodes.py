@@ -150,6 +150,10 @@ def create_generator_node(generator, mode: str = "balanced",
             sampling["seed"] = int(meta["seed"])
         if meta.get("grammar") is not None:     # response_format
             sampling["grammar"] = meta["grammar"]
+        for key in ("repetition_penalty", "frequency_penalty",
+                    "presence_penalty"):
+            if isinstance(meta.get(key), (int, float)):
+                sampling[key] = float(meta[key])
         history = state.get("metadata", {}).get("history") or []
         hist_txt = "".join(
             f"{turn.get('role', 'user')}: {turn.get('content', '')}\n"

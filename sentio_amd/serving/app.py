@@ -67,6 +67,11 @@ class ChatRequest(BaseModel):
     top_p: float | None = Field(default=None, gt=0.0, le=1.0)
     sampling_top_k: int | None = Field(default=None, ge=0)   # 0 = off
     seed: int | None = Field(default=None, ge=0)
+    # penalties over the tokens the answer has emitted so far (the prompt
+    # is not counted); unset fields take GEN_*_PENALTY
+    repetition_penalty: float | None = Field(default=None, gt=0.0, le=10.0)
+    frequency_penalty: float | None = Field(default=None, ge=-2.0, le=2.0)
+    presence_penalty: float | None = Field(default=None, ge=-2.0, le=2.0)
     # constrained decoding: {"type": "regex", "pattern": ...} or
     # {"type": "json_object", "fields": [...]}
     response_format: dict | None = None
@@ -274,7 +279,9 @@ def create_app(settings: Settings | None = None,
             result = await _run_sync(chat_handler.process, req.question,
                                      req.top_k, req.temperature, req.history,
                                      req.top_p, req.sampling_top_k, req.seed,
-                                     grammar)
+                                     grammar, req.repetition_penalty,
+                                     req.frequency_penalty,
+                                     req.presence_penalty)
             performance_monitor.record_value(
                 "chat_latency_ms", (time.perf_counter() - t0) * 1e3)
             return result
@@ -311,7 +318,9 @@ def create_app(settings: Settings | None = None,
             from sentio_amd.serving.handlers import resolve_sampling
 
             sampling = resolve_sampling(s, req.top_p, req.sampling_top_k,
-                                        req.seed)
+                                        req.seed, req.repetition_penalty,
+                                        req.frequency_penalty,
+                                        req.presence_penalty)
             if "sampling_top_k" in sampling:
                 sampling["top_k"] = sampling.pop("sampling_top_k")
             if grammar is not None:

@@ -19,8 +19,8 @@ Three coalescing layers live here:
   path) — wave batching: group by sampling params, keep collecting while
   the engine runs the previous batch, run ONE batched generate.  It also
   serves, beside the continuous loop, the requests the loop does not take
-  (`_SampledItem`): seeded ones always, and top-k / top-p ones unless
-  `slot_sampling` is on.
+  (`_SampledItem`): seeded and penalised ones always, and top-k / top-p
+  ones unless `slot_sampling` is on.
 * `MicroBatcher` + `BatchedEncoder`/`BatchedReranker` — concurrent
   single-query embeds / rerank pair scores coalesce into one engine
   forward each.
@@ -58,6 +58,10 @@ class _Item:
         return (self.temperature, self.max_new_tokens, self.stop_on_eos)
 
 
+_PENALTY_KEYS = ("repetition_penalty", "frequency_penalty", "presence_penalty")
+_NEUTRAL_PENALTIES = (1.0, 0.0, 0.0)
+
+
 @dataclass
 class _SampledItem(_Item):
     """A request with nucleus-sampling controls (top-k / top-p / seed).
@@ -70,12 +74,28 @@ class _SampledItem(_Item):
     # constrained decoding: the engine's GrammarHandle (or a Grammar for a
     # generator that resolves it itself); None for a free-text request
     grammar: Any = None
+    # repetition / frequency / presence penalties; (1, 0, 0) = off.  A
+    # penalised request is a wave request in both slot modes.
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+
+    @property
+    def penalties(self) -> tuple:
+        return (self.repetition_penalty, self.frequency_penalty,
+                self.presence_penalty)
+
+    @property
+    def penalized(self) -> bool:
+        return self.penalties != _NEUTRAL_PENALTIES
 
     @property
     def sampling_kwargs(self) -> dict:
         kw = {"top_k": self.top_k, "top_p": self.top_p, "seed": self.seed}
         if self.grammar is not None:
             kw["grammar"] = self.grammar
+        if self.penalized:
+            kw.update(zip(_PENALTY_KEYS, self.penalties))
         return kw
 
     @property
@@ -86,18 +106,25 @@ class _SampledItem(_Item):
         return (self.temperature, self.max_new_tokens, self.stop_on_eos,
                 self.top_k, self.top_p, self.seed,
                 id(self) if self.seed is not None else None,
-                id(self.grammar) if self.grammar is not None else None)
+                id(self.grammar) if self.grammar is not None else None,
+                *self.penalties)
 
 
 def _make_item(prompt: str, max_new_tokens: int, temperature: float,
                stop_on_eos: bool, stream_q=None, top_k: int = 0,
                top_p: float = 1.0, seed: int | None = None,
-               grammar=None) -> _Item:
+               grammar=None, repetition_penalty: float = 1.0,
+               frequency_penalty: float = 0.0,
+               presence_penalty: float = 0.0) -> _Item:
     top_k, top_p = int(top_k or 0), float(top_p)
-    if top_k > 0 or top_p < 1.0 or seed is not None or grammar is not None:
+    pens = (float(repetition_penalty), float(frequency_penalty),
+            float(presence_penalty))
+    if top_k > 0 or top_p < 1.0 or seed is not None or grammar is not None \
+            or pens != _NEUTRAL_PENALTIES:
         return _SampledItem(prompt, max_new_tokens, float(temperature),
                             stop_on_eos, stream_q=stream_q, top_k=top_k,
-                            top_p=top_p, seed=seed, grammar=grammar)
+                            top_p=top_p, seed=seed, grammar=grammar,
+                            **dict(zip(_PENALTY_KEYS, pens)))
     return _Item(prompt, max_new_tokens, float(temperature), stop_on_eos,
                  stream_q=stream_q)
 
@@ -136,8 +163,8 @@ def _resolve_grammar(generator, grammar, max_new_tokens: int):
 
 def _sampling_only(kwargs: dict) -> dict:
     """The sampling keywords of a frontend call (top_k / top_p / seed /
-    grammar) that take a request off the default path; {} for a default
-    request."""
+    grammar / the three penalties) that take a request off the default
+    path; {} for a default request."""
     out = {}
     if int(kwargs.get("top_k") or 0) > 0:
         out["top_k"] = int(kwargs["top_k"])
@@ -147,6 +174,9 @@ def _sampling_only(kwargs: dict) -> dict:
         out["seed"] = int(kwargs["seed"])
     if kwargs.get("grammar") is not None:
         out["grammar"] = kwargs["grammar"]
+    for key, neutral in zip(_PENALTY_KEYS, _NEUTRAL_PENALTIES):
+        if kwargs.get(key) is not None and float(kwargs[key]) != neutral:
+            out[key] = float(kwargs[key])
     return out
 
 
@@ -167,19 +197,19 @@ class DynamicBatcher:
                  temperature: float = 0.3, stop_on_eos: bool = True,
                  timeout_s: float = 300.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int | None = None,
-                 grammar=None) -> str:
+                 grammar=None, **penalties) -> str:
         grammar = _resolve_grammar(self.generator, grammar, max_new_tokens)
         self.start()
         item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
                           top_k=top_k, top_p=top_p, seed=seed,
-                          grammar=grammar)
+                          grammar=grammar, **penalties)
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
 
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
                         temperature: float = 0.3, timeout_s: float = 300.0,
                         top_k: int = 0, top_p: float = 1.0,
-                        seed: int | None = None, grammar=None):
+                        seed: int | None = None, grammar=None, **penalties):
         """Yield text deltas token-by-token.  The request JOINS batched
         decode (continuous-batching-lite: it occupies a batch slot and its
         token ids stream out per decode step); concurrent non-stream chat
@@ -189,7 +219,7 @@ class DynamicBatcher:
         self.start()
         item = _make_item(prompt, max_new_tokens, temperature, True,
                           stream_q=queue.Queue(), top_k=top_k, top_p=top_p,
-                          seed=seed, grammar=grammar)
+                          seed=seed, grammar=grammar, **penalties)
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
 
@@ -345,7 +375,10 @@ class ContinuousBatcher:
     make a slot-loop answer reproducible (ContinuousGenerator keeps seeded
     requests on the wave path for that reason).  Off (the default): the
     loop samples with per-row temperature only, through sample_rows, and
-    rejects requests that set top_k / top_p / seed."""
+    rejects requests that set top_k / top_p / seed.  A request with a
+    repetition / frequency / presence penalty is rejected in both modes:
+    the slot loop keeps no per-slot token history for ops.sample_penalized
+    (ContinuousGenerator runs such requests as waves)."""
 
     def __init__(self, generator, slots: int = 32, admit_max: int = 8,
                  slot_sampling: bool = False):
@@ -362,11 +395,16 @@ class ContinuousBatcher:
 
     # ----- caller side -----
     def _item(self, prompt, max_new_tokens, temperature, stop_on_eos,
-              stream_q, top_k, top_p, seed, grammar=None) -> _Item:
+              stream_q, top_k, top_p, seed, grammar=None,
+              **penalties) -> _Item:
         grammar = _resolve_grammar(self.generator, grammar, max_new_tokens)
         item = _make_item(prompt, max_new_tokens, temperature, stop_on_eos,
                           stream_q=stream_q, top_k=top_k, top_p=top_p,
-                          seed=seed, grammar=grammar)
+                          seed=seed, grammar=grammar, **penalties)
+        if isinstance(item, _SampledItem) and item.penalized:
+            raise ValueError(
+                "repetition / frequency / presence penalties are not served "
+                "by the continuous slot loop: they run as waves")
         if isinstance(item, _SampledItem) and not self.slot_sampling:
             raise ValueError(
                 "top_k / top_p / seed / grammar need ContinuousBatcher("
@@ -378,9 +416,9 @@ class ContinuousBatcher:
                  temperature: float = 0.3, stop_on_eos: bool = True,
                  timeout_s: float = 300.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int | None = None,
-                 grammar=None) -> str:
+                 grammar=None, **penalties) -> str:
         item = self._item(prompt, max_new_tokens, temperature, stop_on_eos,
-                          None, top_k, top_p, seed, grammar)
+                          None, top_k, top_p, seed, grammar, **penalties)
         self.start()
         self._q.put(item)
         return item.future.result(timeout=timeout_s)
@@ -388,9 +426,10 @@ class ContinuousBatcher:
     def generate_stream(self, prompt: str, max_new_tokens: int = 128,
                         temperature: float = 0.3, timeout_s: float = 300.0,
                         top_k: int = 0, top_p: float = 1.0,
-                        seed: int | None = None, grammar=None):
+                        seed: int | None = None, grammar=None, **penalties):
         item = self._item(prompt, max_new_tokens, temperature, True,
-                          queue.Queue(), top_k, top_p, seed, grammar)
+                          queue.Queue(), top_k, top_p, seed, grammar,
+                          **penalties)
         self.start()
         self._q.put(item)
         from sentio_amd.engines.tokenizer import EOS_ID
@@ -718,7 +757,9 @@ class ContinuousGenerator:
     the same answer whatever else shares the engine, and in the slot loop a
     request's logits come from a different row of a shared batch on each
     run, where nothing guarantees bitwise-equal GEMM rows across row
-    positions -- the loop cannot keep that promise."""
+    positions -- the loop cannot keep that promise.  So do requests with a
+    repetition / frequency / presence penalty: the loop keeps no per-slot
+    token history, and the three values are part of the wave key."""
 
     def __init__(self, raw, slots: int = 32, slot_sampling: bool = False):
         self.raw = raw
@@ -730,8 +771,9 @@ class ContinuousGenerator:
     def _joins_loop(self, sampling: dict) -> bool:
         """Whether a single-prompt request with these sampling keywords
         ({} for a default one) goes to the slot loop."""
-        return not sampling or (self.slot_sampling
-                                and "seed" not in sampling)
+        return not sampling or (
+            self.slot_sampling and "seed" not in sampling
+            and not any(k in sampling for k in _PENALTY_KEYS))
 
     def generate(self, prompts: list[str], max_new_tokens: int = 128,
                  temperature: float = 0.3, stop_on_eos: bool = True,

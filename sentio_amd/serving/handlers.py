@@ -21,11 +21,16 @@ logger = logging.getLogger(__name__)
 
 def resolve_sampling(settings, top_p: float | None = None,
                      sampling_top_k: int | None = None,
-                     seed: int | None = None) -> dict[str, Any]:
-    """Request-level nucleus sampling controls as pipeline metadata.  A field
-    the request leaves unset takes the service-wide default (GEN_TOP_P /
-    GEN_TOP_K); values that switch a filter off are dropped, so a request
-    with nothing set yields {} and stays on the default sampling path."""
+                     seed: int | None = None,
+                     repetition_penalty: float | None = None,
+                     frequency_penalty: float | None = None,
+                     presence_penalty: float | None = None) -> dict[str, Any]:
+    """Request-level sampling controls as pipeline metadata.  A field the
+    request leaves unset takes the service-wide default (GEN_TOP_P /
+    GEN_TOP_K / GEN_REPETITION_PENALTY / GEN_FREQUENCY_PENALTY /
+    GEN_PRESENCE_PENALTY); values that switch a control off are dropped, so
+    a request with nothing set yields {} and stays on the default sampling
+    path."""
     p = top_p if top_p is not None else getattr(settings, "gen_top_p", 1.0)
     k = sampling_top_k if sampling_top_k is not None \
         else getattr(settings, "gen_top_k", 0)
@@ -38,6 +43,14 @@ def resolve_sampling(settings, top_p: float | None = None,
         out["sampling_top_k"] = int(k)
     if seed is not None:
         out["seed"] = int(seed)
+    for key, value, neutral in (
+            ("repetition_penalty", repetition_penalty, 1.0),
+            ("frequency_penalty", frequency_penalty, 0.0),
+            ("presence_penalty", presence_penalty, 0.0)):
+        if value is None:
+            value = getattr(settings, "gen_" + key, neutral)
+        if value is not None and float(value) != neutral:
+            out[key] = float(value)
     return out
 
 
@@ -131,16 +144,20 @@ class ChatHandler:
                 top_p: float | None = None,
                 sampling_top_k: int | None = None,
                 seed: int | None = None,
-                grammar=None) -> dict[str, Any]:
-        """top_k is the RETRIEVAL depth; sampling_top_k / top_p / seed are
-        the generator's sampling controls; grammar (a compiled
-        response_format) constrains the answer."""
+                grammar=None,
+                repetition_penalty: float | None = None,
+                frequency_penalty: float | None = None,
+                presence_penalty: float | None = None) -> dict[str, Any]:
+        """top_k is the RETRIEVAL depth; sampling_top_k / top_p / seed and
+        the three penalties are the generator's sampling controls; grammar
+        (a compiled response_format) constrains the answer."""
         query_id = str(uuid.uuid4())
         meta: dict[str, Any] = {"query_id": query_id}
         if grammar is not None:
             meta["grammar"] = grammar
         meta.update(resolve_sampling(getattr(self.container, "settings", None), top_p,
-                                     sampling_top_k, seed))
+                                     sampling_top_k, seed, repetition_penalty,
+                                     frequency_penalty, presence_penalty))
         if top_k is not None:
             meta["user_top_k"] = int(top_k)
         if temperature is not None:
