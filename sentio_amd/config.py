@@ -108,6 +108,8 @@ class Settings:
     kv_cache_dtype: str = "bf16"            # bf16 | fp8 (e4m3fn session KV cache)
     dense_index_dtype: str = "fp16"         # fp16 | fp8 (e4m3fn codes + a scale per row)
     dense_filter: str = "post"              # post | exact (masked scan: exact filtered dense search)
+    dense_mmr_lambda: float | None = None   # unset: off; in [0, 1]: dense hits diversified by MMR (1 = relevance only)
+    dense_mmr_fetch_k: int | None = None    # MMR candidates per query, in [1, 128] (unset: min(max(4 * top_k, 32), 128))
     bm25_search: str = "scores"             # scores | fused (batched BM25 scoring with the top-k in the kernel)
     spec_decode_tokens: int = 0             # prompt-lookup draft tokens per decode step (0: off)
     max_batch_size: int = 64          # continuous-batching slots (64 rows of KV ~ 68 GB at 8k ctx)
@@ -170,6 +172,8 @@ class Settings:
         "kv_cache_dtype": "KV_CACHE_DTYPE",
         "dense_index_dtype": "DENSE_INDEX_DTYPE",
         "dense_filter": "DENSE_FILTER",
+        "dense_mmr_lambda": "DENSE_MMR_LAMBDA",
+        "dense_mmr_fetch_k": "DENSE_MMR_FETCH_K",
         "bm25_search": "BM25_SEARCH",
         "spec_decode_tokens": "SPEC_DECODE_TOKENS",
         "max_batch_size": "MAX_BATCH_SIZE",
@@ -195,6 +199,8 @@ class Settings:
             if env is None or os.getenv(env) is None:
                 continue
             cur = getattr(s, f.name)
+            if cur is None:                      # optional numbers, below
+                continue
             if isinstance(cur, bool):
                 setattr(s, f.name, _env_bool(env, cur))
             elif isinstance(cur, int):
@@ -212,6 +218,23 @@ class Settings:
         if s.dense_filter not in ("post", "exact"):
             raise ValueError("DENSE_FILTER must be post or exact, got "
                              f"{s.dense_filter!r}")
+        for name, conv in (("dense_mmr_lambda", float),
+                           ("dense_mmr_fetch_k", int)):
+            raw = (os.getenv(cls._ENV_MAP[name]) or "").strip()
+            if raw:
+                try:
+                    setattr(s, name, conv(raw))
+                except ValueError:
+                    raise ValueError(f"{cls._ENV_MAP[name]} must be a number, "
+                                     f"got {raw!r}") from None
+        if s.dense_mmr_lambda is not None and \
+                not 0.0 <= s.dense_mmr_lambda <= 1.0:
+            raise ValueError("DENSE_MMR_LAMBDA must be in [0, 1], got "
+                             f"{s.dense_mmr_lambda}")
+        if s.dense_mmr_fetch_k is not None and \
+                not 1 <= s.dense_mmr_fetch_k <= 128:
+            raise ValueError("DENSE_MMR_FETCH_K must be in [1, 128], got "
+                             f"{s.dense_mmr_fetch_k}")
         if s.bm25_search not in ("scores", "fused"):
             raise ValueError("BM25_SEARCH must be scores or fused, got "
                              f"{s.bm25_search!r}")

@@ -23,6 +23,11 @@ search: the filter becomes a row bit mask (built on the host from the
 payloads, cached per filter, extended as rows are added) and
 ops.cosine_topk_masked selects top_k among the allowed rows only.
 search_rows(allow=...) takes such masks directly, one per query if wanted.
+
+search(..., mmr_lambda=...) (opt-in) diversifies: fetch_k candidates come
+from the path the search would take anyway and ops.mmr_select picks top_k of
+them by maximal marginal relevance, from the rows stored here (one kernel:
+their Gram matrix on MFMA and the greedy picks).
 """
 
 from __future__ import annotations
@@ -136,15 +141,32 @@ class DenseIndex:
     def search(
         self, query: torch.Tensor, top_k: int,
         metadata_filter: dict | None = None,
+        *, mmr_lambda: float | None = None, fetch_k: int | None = None,
     ) -> list[list[tuple[str, float]]]:
         """Batched cosine top-k.  query: [B, dim] or [dim].
         metadata_filter: equality conditions on document metadata (the
         reference's Qdrant FieldCondition filters, qdrant_store.py:456-471)
-        applied as a post-filter over an over-fetched candidate set."""
+        applied as a post-filter over an over-fetched candidate set.
+        mmr_lambda in [0, 1]: return top_k of the fetch_k nearest rows
+        (default min(max(4 * top_k, 32), 128, size)) picked by maximal
+        marginal relevance, in pick order; the scores stay cosines.  With a
+        metadata_filter this needs filter_mode="exact"."""
         if query.ndim == 1:
             query = query.unsqueeze(0)
         if self._size == 0:
             return [[] for _ in range(query.shape[0])]
+        if mmr_lambda is not None:
+            if metadata_filter and self.filter_mode != "exact":
+                raise ValueError("mmr_lambda with a metadata_filter needs "
+                                 'filter_mode="exact"')
+            q = query.to(self.device, torch.float32)
+            q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
+            allow = self._filter_mask(metadata_filter) \
+                if metadata_filter else None
+            vals, idx = self._topk_mmr(q, top_k, allow, mmr_lambda, fetch_k)
+            return [[(self.doc_ids[i], float(v)) for v, i in zip(vr, ir)
+                     if i >= 0]
+                    for vr, ir in zip(vals.cpu().tolist(), idx.cpu().tolist())]
         if metadata_filter and self.filter_mode == "exact":
             q = query.to(self.device, torch.float32)
             q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
@@ -183,7 +205,9 @@ class DenseIndex:
         return out
 
     def search_rows(self, query: torch.Tensor, top_k: int,
-                    allow: torch.Tensor | None = None
+                    allow: torch.Tensor | None = None,
+                    *, mmr_lambda: float | None = None,
+                    fetch_k: int | None = None
                     ) -> tuple[torch.Tensor, torch.Tensor]:
         """Tensor-only batched cosine top-k: (scores [B,k] f32, rows [B,k]
         i64), padded with (-inf, -1) when the shard holds fewer than top_k
@@ -191,7 +215,8 @@ class DenseIndex:
         directly (no pickled objects on the query hot path).
         allow: int32 [1 or B, W] row mask on the index device
         (ops.pack_row_mask), one for all queries or one per query: the
-        search runs over the allowed rows only, in either filter_mode."""
+        search runs over the allowed rows only, in either filter_mode.
+        mmr_lambda, fetch_k: as in search(); rows come in pick order."""
         if query.ndim == 1:
             query = query.unsqueeze(0)
         B = query.shape[0]
@@ -199,6 +224,10 @@ class DenseIndex:
             return (torch.full((B, top_k), float("-inf"), device=self.device),
                     torch.full((B, top_k), -1, dtype=torch.int64,
                                device=self.device))
+        if mmr_lambda is not None:
+            q = query.to(self.device, torch.float32)
+            q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
+            return self._topk_mmr(q, top_k, allow, mmr_lambda, fetch_k)
         k = min(top_k, self._size)
         q = query.to(self.device, torch.float32)
         q = q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)
@@ -262,6 +291,53 @@ class DenseIndex:
                                           k, allow.contiguous())
         qq = q.to(torch.float16) if self.fp8 else q
         return torch_ref.cosine_topk_masked(qq, rows, scales, k, allow)
+
+    def _topk_mmr(self, q: torch.Tensor, top_k: int,
+                  allow: torch.Tensor | None, lam: float,
+                  fetch_k: int | None) -> tuple[torch.Tensor, torch.Tensor]:
+        """top_k of the fetch_k nearest (allowed) rows for normalised fp32
+        queries, picked by maximal marginal relevance over the stored rows;
+        (cosine, row) in pick order, padded with (-inf, -1).  The candidates
+        come from the path a plain search takes; ops.mmr_select serves GPU
+        fp8 and fp16 indexes at dim % 32 == 0 and dim <= 1024, any other
+        shape and the CPU take the reference.  No host sync."""
+        from sentio_amd import ops
+        from sentio_amd.ops import torch_ref
+
+        n, lam = self._size, float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must be in [0, 1], got {lam}")
+        if fetch_k is None:
+            fetch_k = min(max(4 * top_k, 32), 128)
+        if not 1 <= top_k <= fetch_k <= 128:
+            raise ValueError("mmr needs 1 <= top_k <= fetch_k <= 128, got "
+                             f"top_k {top_k}, fetch_k {fetch_k}")
+        fetch = min(fetch_k, n)
+        if allow is not None:
+            _, cand = self._topk_masked(q, fetch, allow)
+        elif self.fp8:
+            _, cand = self._topk_fp8(q, fetch)
+        elif self.device != "cpu":
+            _, cand = ops.cosine_topk(q.to(self.dtype), self._vecs[:n], fetch)
+        else:
+            _, cand = torch.topk(q @ self._vecs[:n].T.float(), fetch, dim=1)
+        cand = cand.long().contiguous()
+        k = min(top_k, fetch)
+        rows = self._codes[:n] if self.fp8 else self._vecs[:n]
+        scales = self._scales[:n] if self.fp8 else None
+        if self.device != "cpu" and ops.fp8_index_dim_ok(self.dim) \
+                and (self.fp8 or self.dtype == torch.float16):
+            vals, idx = ops.mmr_select(q.to(torch.float16), rows, scales,
+                                       cand, k, lam)
+        else:
+            qq = q.to(torch.float16) if self.fp8 else q
+            vals, idx = torch_ref.mmr_select(qq, rows, scales, cand, k, lam)
+        if k < top_k:
+            B = q.shape[0]
+            vals = torch.cat([vals, vals.new_full((B, top_k - k),
+                                                  float("-inf"))], 1)
+            idx = torch.cat([idx, idx.new_full((B, top_k - k), -1)], 1)
+        return vals, idx
 
     def _filter_mask(self, metadata_filter: dict) -> torch.Tensor:
         """The filter's int32 [1, W] row mask on the index device.  The

@@ -643,6 +643,62 @@ def cosine_topk_masked(q, rows, scales, k: int, allow):
     return torch_ref.cosine_topk_masked(q, rows, scales, k, allow)
 
 
+MMR_MAX_CANDIDATES = 128
+
+
+def mmr_select(q, rows, scales, cand, k: int, lam: float):
+    """Maximal-marginal-relevance selection over candidate lists, the Gram
+    matrix and the greedy picks in one kernel, from the rows the index
+    stores.  q fp16 [B, D]; rows and scales as in cosine_topk_masked (uint8
+    e4m3fn codes [N, D] with scales fp32 [N], or fp16 [N, D] with scales
+    None); cand int64 [B, C]: index rows as a top-k kernel returns them,
+    unique within a list, -1 padding at the tail.  1 <= C <= 128, 1 <= k <=
+    C, D % 32 == 0 and D <= 1024, 0 <= lam <= 1, any B.  Step t picks the
+    unpicked candidate with the largest lam * cos(q, d) - (1 - lam) * max
+    over the picks s of cos(d, s), a tie to the lower position.  Returns
+    (cosine to the query f32 [B, k], index rows i64 [B, k]) in pick order,
+    padded with (-inf, -1) past the valid candidates; the same inputs give
+    the same bits (torch_ref.mmr_select is the spec and the CPU path).  No
+    host sync; nothing is converted or copied: a bad shape, dtype, device,
+    alignment, k, C, D or lam raises ValueError before a launch."""
+    args = [("q", q, torch.float16, 2),
+            ("rows", rows, torch.float16 if scales is None else torch.uint8, 2),
+            ("cand", cand, torch.int64, 2)]
+    if scales is not None:
+        args.append(("scales", scales, torch.float32, 1))
+    for name, t, dt, nd in args:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd \
+                or t.numel() == 0 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a non-empty contiguous {dt} "
+                             f"{nd}-d tensor")
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, q on {q.device}")
+    N, C = rows.shape[0], cand.shape[1]
+    if rows.shape[1] != q.shape[1] or cand.shape[0] != q.shape[0] or \
+            (scales is not None and scales.shape[0] != N):
+        raise ValueError(f"q {tuple(q.shape)}, rows {tuple(rows.shape)}, cand "
+                         f"{tuple(cand.shape)} and scales do not agree")
+    if not fp8_index_dim_ok(q.shape[1]):
+        raise ValueError("mmr_select serves dim % 32 == 0 and dim <= 1024, "
+                         f"got {q.shape[1]}")
+    if N >= 2 ** 31:
+        raise ValueError(f"rows must hold fewer than 2^31 rows, got {N}")
+    if C > MMR_MAX_CANDIDATES:
+        raise ValueError(f"at most {MMR_MAX_CANDIDATES} candidates per list, "
+                         f"got {C}")
+    k, lam = int(k), float(lam)
+    if not 1 <= k <= C:
+        raise ValueError(f"k must be in [1, {C}], got {k}")
+    if not 0.0 <= lam <= 1.0:                      # NaN fails too
+        raise ValueError(f"lam must be in [0, 1], got {lam}")
+    if any(t.data_ptr() % 16 for t in (q, rows)):
+        raise ValueError("q and rows must be 16-byte aligned")
+    if _on_gpu(q):
+        vals, idx = _require_hip().mmr_select(q, rows, scales, cand, k, lam)
+        return vals, idx
+    return torch_ref.mmr_select(q, rows, scales, cand, k, lam)
+
+
 def cosine_scores(q, mat):
     """Hand wave-per-row scan (LDS-staged queries); B*D*4 must fit in LDS."""
     if _on_gpu(q, mat):
@@ -1291,6 +1347,6 @@ def gemm_bf16(a, b):
 
 __all__ = [
     "rmsnorm", "rmsnorm_residual", "rope_apply", "decode_qkv_prep", "prefill_qkv_prep","decode_attention_fused", "decode_attention_verify", "ngram_draft", "spec_accept", "decode_attention_fused_fp8", "kv_store_fp8", "swiglu", "swiglu_packed", "softmax",
-    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok", "cosine_topk_masked", "pack_row_mask",
+    "attention", "attention_cache", "decode_attention", "decode_attention_bmm", "mean_pool_l2norm", "cosine_topk", "cosine_topk_fp8", "cosine_topk_fp8_plan", "fp8_index_dim_ok", "cosine_topk_masked", "pack_row_mask", "mmr_select",
     "bm25_score", "cosine_scores", "fuse_topk", "lt_linear", "linear_splitk", "decode_gemm_plan", "rmsnorm_residual_partials", "sample_token", "sample_filtered", "sample_slots", "sample_penalized", "check_penalties", "sample_support", "sample_constrained", "sample_slots_constrained", "GrammarTables", "gemm_bf16", "skinny_gemm", "hip_available", "torch_ref",
 ]

@@ -646,6 +646,45 @@ std::vector<torch::Tensor> cosine_topk_masked(
   return {out_s, out_r};
 }
 
+// MMR selection over candidate lists (Gram matrix and greedy picks in one
+// kernel); the Python wrapper has checked the arguments.  No host sync.
+std::vector<torch::Tensor> mmr_select(
+    torch::Tensor q, torch::Tensor rows, c10::optional<torch::Tensor> scales,
+    torch::Tensor cand, int64_t k, double lam) {
+  TORCH_CHECK(q.is_cuda() && rows.is_cuda() && cand.is_cuda() &&
+              (!scales.has_value() || scales->is_cuda()),
+              "mmr_select: tensors must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kHalf && q.dim() == 2 &&
+              q.is_contiguous(), "q must be contiguous fp16 [B, D]");
+  TORCH_CHECK(rows.scalar_type() ==
+                  (scales.has_value() ? torch::kByte : torch::kHalf) &&
+              rows.dim() == 2 && rows.is_contiguous() &&
+              rows.size(1) == q.size(1),
+              "rows must be contiguous uint8 (with scales) or fp16 [N, D]");
+  const long N = rows.size(0), B = q.size(0);
+  if (scales.has_value())
+    TORCH_CHECK(scales->scalar_type() == torch::kFloat && scales->dim() == 1 &&
+                scales->is_contiguous() && scales->size(0) == N,
+                "scales must be contiguous fp32 [N]");
+  TORCH_CHECK(cand.scalar_type() == torch::kLong && cand.dim() == 2 &&
+              cand.is_contiguous() && cand.size(0) == B && cand.size(1) >= 1,
+              "cand must be contiguous int64 [B, C]");
+  TORCH_CHECK(N >= 1 && B >= 1 && k >= 1 && k <= cand.size(1),
+              "mmr_select: empty input or k out of range");
+  auto f32 = q.options().dtype(torch::kFloat);
+  auto out_s = torch::empty({B, k}, f32);
+  auto out_r = torch::empty({B, k}, f32.dtype(torch::kLong));
+  check_hip(sentio_mmr_select(
+                q.data_ptr(), rows.data_ptr(),
+                scales.has_value() ? scales->data_ptr<float>() : nullptr,
+                (const long*)cand.data_ptr<int64_t>(),
+                out_s.data_ptr<float>(), (long*)out_r.data_ptr<int64_t>(), N,
+                (int)q.size(1), (int)B, (int)cand.size(1), (int)k, (float)lam,
+                stream()),
+            "mmr_select");
+  return {out_s, out_r};
+}
+
 torch::Tensor bm25_score(torch::Tensor term_ids, torch::Tensor indptr,
                          torch::Tensor post_doc, torch::Tensor post_tf,
                          torch::Tensor idf, torch::Tensor doc_len,
@@ -1191,6 +1230,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk_fp8", &cosine_topk_fp8);
   m.def("cosine_topk_fp8_plan", &cosine_topk_fp8_plan);
   m.def("cosine_topk_masked", &cosine_topk_masked);
+  m.def("mmr_select", &mmr_select);
   m.def("bm25_score", &bm25_score);
   m.def("bm25_topk", &bm25_topk);
   m.def("bm25_topk_plan", &bm25_topk_plan);

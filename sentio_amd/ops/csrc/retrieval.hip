@@ -1195,7 +1195,279 @@ IDX_NO_PK_F32 __global__ void bm25_topk_kernel(
   }
 }
 
+// ------------------------- MMR: fused Gram matrix and greedy selection
+// mmr_select_kernel diversifies the candidate list of one query per block
+// (8 waves): cand int64 [B, C], C <= 128, the rows a top-k kernel returned,
+// -1 padding at the tail (a row outside [0, N) counts as padding).  All
+// similarities come from the stored rows, fp16 or e4m3fn codes with a scale
+// per row: rel_i = x_i . q and S_ij = x_i . x_j, fp32 sums of fp16 products
+// (codes are multiplied unscaled, the scales multiply the finished sums).
+//
+// Gram phase.  D is walked in slabs of 128 dims.  Wave w gathers the slab of
+// candidates 16w .. 16w+15: lane (c = l & 15, g = l >> 4) loads 16 bytes of
+// row c per unit, four lanes covering 64 contiguous bytes, zeros for a
+// padding row and past D.  For fp16 the four loads of a lane are its four A
+// operands of mfma_f32_16x16x32_f16 (k = s*32 + g*8) as they stand; for
+// e4m3fn two loads become four operands through idx_cvt8, which permutes k
+// inside the slab.  The contraction order is free as long as every row and
+// the query use the same one, and they do: a lane writes its operands to an
+// LDS image [129 rows][128 halves, stride 272 B] at (row, s*64 + g*16), the
+// query slab goes to row 128 through the same permutation, and every B
+// operand is one conflict-free 16-byte read of that image.  The image is
+// double-buffered: one block barrier per slab, the next slab's global loads
+// issued before the barrier and in flight over the MFMAs.  Wave w owns row
+// tile w against every column tile and the query (column 0 of a ninth
+// tile): at most nine accumulators.  Tiles past the last valid candidate
+// are skipped, loads and MFMAs alike.  The whole matrix is computed, not
+// its upper triangle: that keeps the eight waves in step between barriers
+// and leaves S complete, so the greedy phase reads rows only.
+//
+// Greedy phase.  The accumulators go to LDS over the dead images, S fp32
+// [128][132] and rel [128], and wave 0 alone runs the k picks: lane l owns
+// candidates l and l + 64 (rel, red and an open flag in registers), a pick
+// is a wave arg-max over (objective desc, position asc), the update reads
+// row p of S (contiguous: no bank conflict; S is symmetric) and the picks
+// stay in registers, pick t in lane t & 63, until one coalesced store
+// after the loop.  No atomics anywhere: the same inputs give the same bits.
+#define MMR_CMAX 128
+#define MMR_SLAB 128                           // dims of a slab
+#define MMR_ROWB (MMR_SLAB * 2 + 16)           // image row stride, bytes
+#define MMR_IMG ((MMR_CMAX + 1) * MMR_ROWB)    // candidates + the query
+#define MMR_SLD (MMR_CMAX + 4)                 // S row stride, floats
+#define MMR_LDS (2 * MMR_IMG + 3 * MMR_CMAX * 4 + 16)
+static_assert(MMR_CMAX * MMR_SLD * 4 <= 2 * MMR_IMG, "S overlays the images");
+static_assert(MMR_CMAX == IDX_WAVES * 16 && MMR_CMAX == 2 * WAVE,
+              "a row tile per wave, two candidates per lane");
+
+template <bool F16>
+__launch_bounds__(IDX_WAVES * WAVE)
+IDX_NO_PK_F32 __global__ void mmr_select_kernel(
+    const char* __restrict__ rows, const float* __restrict__ scales,
+    const _Float16* __restrict__ q, const long* __restrict__ cand,
+    float* __restrict__ out_s, long* __restrict__ out_r, long N, int D, int C,
+    int k, float lam, float oml) {
+  constexpr int R = F16 ? 4 : 2;               // 16-byte loads per slab
+  constexpr int EB = F16 ? 2 : 1;              // bytes per element
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* S = reinterpret_cast<float*>(smem);   // over the images, later
+  float* rel = reinterpret_cast<float*>(smem + 2 * MMR_IMG);   // [128]
+  float* sscale = rel + MMR_CMAX;                               // [128]
+  int* crow = reinterpret_cast<int*>(sscale + MMR_CMAX);       // [128]
+  unsigned long long* vmask =
+      reinterpret_cast<unsigned long long*>(crow + MMR_CMAX);  // [2]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int w = tid / WAVE;
+  const int c = lane & 15, g = lane >> 4;
+  const long b = blockIdx.x;
+
+  if (tid < MMR_CMAX) {
+    long r = -1;
+    if (tid < C) r = cand[b * C + tid];
+    const bool ok = r >= 0 && r < N;
+    crow[tid] = ok ? (int)r : -1;
+    float sc = 1.f;
+    if constexpr (!F16) sc = ok ? scales[r] : 0.f;
+    sscale[tid] = sc;
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) vmask[w] = bal;
+  }
+  __syncthreads();
+  const unsigned long long v0 = vmask[0], v1 = vmask[1];
+  // candidates up to the last valid one, in 16-row tiles
+  const int nv = v1 ? 128 - __clzll((long long)v1)
+                    : (v0 ? 64 - __clzll((long long)v0) : 0);
+  const int NT = (nv + 15) >> 4;
+  const bool live = w < NT;                    // wave-uniform
+  const int myrow = crow[16 * w + c];
+  const char* rp = rows + (long)(myrow < 0 ? 0 : myrow) * D * EB;
+  const _Float16* qp = q + b * D;
+  const int NSL = (D + MMR_SLAB - 1) / MMR_SLAB;
+
+  // this lane's 16-byte units of a slab, and (first 16 threads) the query's;
+  // the query unit of thread s*4 + g lands where operand s of lane group g
+  // does, so it reads the k that the rows' permutation puts there
+  // (the lambda must inline: a call would put the captures in scratch)
+  auto load = [&](int slab, u32x4_t (&raw)[R], u32x4_t& qraw)
+                  __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      raw[j] = u32x4_t{0u, 0u, 0u, 0u};
+      const int k0 = slab * MMR_SLAB + (F16 ? j * 32 + g * 8 : j * 64 + g * 16);
+      if (live && myrow >= 0 && k0 < D)
+        raw[j] = *reinterpret_cast<const u32x4_t*>(rp + (long)k0 * EB);
+    }
+    qraw = u32x4_t{0u, 0u, 0u, 0u};
+    if (tid < 16) {
+      const int s = tid >> 2, gq = tid & 3;
+      const int kq = slab * MMR_SLAB +
+                     (F16 ? s * 32 + gq * 8
+                          : (s >> 1) * 64 + gq * 16 + (s & 1) * 8);
+      if (kq < D) qraw = *reinterpret_cast<const u32x4_t*>(qp + kq);
+    }
+  };
+
+  f32x4 acc[IDX_WAVES + 1];
+#pragma unroll
+  for (int t = 0; t <= IDX_WAVES; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  u32x4_t raw[R], qraw;
+  load(0, raw, qraw);
+  for (int slab = 0; slab < NSL; ++slab) {
+    char* im = smem + (slab & 1) * MMR_IMG;
+    f16x8_t a[4];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      if constexpr (F16) {
+        a[j] = __builtin_bit_cast(f16x8_t, raw[j]);
+      } else {
+        a[2 * j] = idx_cvt8(raw[j].x, raw[j].y);
+        a[2 * j + 1] = idx_cvt8(raw[j].z, raw[j].w);
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        *reinterpret_cast<f16x8_t*>(im + (16 * w + c) * MMR_ROWB + s * 64 +
+                                    g * 16) = a[s];
+    }
+    if (tid < 16)
+      *reinterpret_cast<u32x4_t*>(im + MMR_CMAX * MMR_ROWB + tid * 16) = qraw;
+    if (slab + 1 < NSL) load(slab + 1, raw, qraw);
+    __syncthreads();
+    if (live) {
+      // operands that hold data: fp16 k runs on, a 64-code unit of e4m3fn
+      // spreads over two operands
+      const int left = D - slab * MMR_SLAB;
+      const int nst = min(4, F16 ? left / 32 : 2 * ((left + 63) / 64));
+      const char* bp = im + c * MMR_ROWB + g * 16;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (s < nst) {
+#pragma unroll
+          for (int t = 0; t < IDX_WAVES; ++t) {
+            if (t < NT) {
+              const f16x8_t bf = *reinterpret_cast<const f16x8_t*>(
+                  bp + t * 16 * MMR_ROWB + s * 64);
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], bf, acc[t],
+                                                              0, 0, 0);
+            }
+          }
+          u32x4_t qb = {0u, 0u, 0u, 0u};
+          if (c == 0)
+            qb = *reinterpret_cast<const u32x4_t*>(
+                im + MMR_CMAX * MMR_ROWB + s * 64 + g * 16);
+          acc[IDX_WAVES] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+              a[s], __builtin_bit_cast(f16x8_t, qb), acc[IDX_WAVES], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // lane (c, g) holds S[16w + 4g + r][16t + c] and, for c == 0, rel
+  __syncthreads();                             // the images are dead
+  if (live) {
+    float si[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) si[r] = sscale[16 * w + 4 * g + r];
+#pragma unroll
+    for (int t = 0; t < IDX_WAVES; ++t) {
+      if (t < NT) {
+        const float sj = sscale[16 * t + c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          S[(16 * w + 4 * g + r) * MMR_SLD + 16 * t + c] =
+              F16 ? acc[t][r] : acc[t][r] * (si[r] * sj);
+      }
+    }
+    if (c == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        rel[16 * w + 4 * g + r] =
+            F16 ? acc[IDX_WAVES][r] : acc[IDX_WAVES][r] * si[r];
+    }
+  }
+  __syncthreads();
+  if (w != 0) return;
+
+  // greedy picks: no block barrier and no global traffic inside the loop
+  bool open0 = (v0 >> lane) & 1ull, open1 = (v1 >> lane) & 1ull;
+  const float rel0 = open0 ? rel[lane] : 0.f;
+  const float rel1 = open1 ? rel[lane + WAVE] : 0.f;
+  float red0 = 0.f, red1 = 0.f;
+  float ps0 = -INFINITY, ps1 = -INFINITY;      // picks lane and lane + 64
+  int pp0 = -1, pp1 = -1;
+  for (int t = 0; t < k; ++t) {
+    // a closed candidate is (-inf, 255); an open one is never below the
+    // largest negative float (NaN included), so it wins over a closed one
+    float o0 = lam * rel0 - oml * red0, o1 = lam * rel1 - oml * red1;
+    if (!(o0 >= -__FLT_MAX__)) o0 = -__FLT_MAX__;
+    if (!(o1 >= -__FLT_MAX__)) o1 = -__FLT_MAX__;
+    float best = open0 ? o0 : -INFINITY;
+    int pos = open0 ? lane : 255;
+    if (open1 && (!open0 || o1 > o0)) {
+      best = o1;
+      pos = lane + WAVE;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ob = __shfl_xor(best, off, WAVE);
+      const int op = __shfl_xor(pos, off, WAVE);
+      if (ob > best || (ob == best && op < pos)) {
+        best = ob;
+        pos = op;
+      }
+    }
+    const int p = __builtin_amdgcn_readfirstlane(pos);
+    if (p >= MMR_CMAX) break;                  // none left: the rest is padding
+    if (lane == (t & (WAVE - 1))) {
+      if (t < WAVE) {
+        ps0 = rel[p];
+        pp0 = crow[p];
+      } else {
+        ps1 = rel[p];
+        pp1 = crow[p];
+      }
+    }
+    if (p == lane) open0 = false;
+    if (p == lane + WAVE) open1 = false;
+    red0 = fmaxf(red0, S[p * MMR_SLD + lane]);
+    red1 = fmaxf(red1, S[p * MMR_SLD + lane + WAVE]);
+  }
+  if (lane < k) {
+    out_s[b * k + lane] = ps0;
+    out_r[b * k + lane] = pp0;
+  }
+  if (lane + WAVE < k) {
+    out_s[b * k + lane + WAVE] = ps1;
+    out_r[b * k + lane + WAVE] = pp1;
+  }
+}
+
 extern "C" {
+
+hipError_t sentio_mmr_select(const void* q, const void* rows,
+                             const float* scales, const long* cand,
+                             float* out_s, long* out_r, long N, int D, int B,
+                             int C, int k, float lam, hipStream_t stream) {
+  if (N < 1 || N > 0x7fffffffL || D < 32 || D > 1024 || D % 32 || B < 1 ||
+      C < 1 || C > MMR_CMAX || k < 1 || k > C || !(lam >= 0.f && lam <= 1.f) ||
+      reinterpret_cast<uintptr_t>(q) % 16 ||
+      reinterpret_cast<uintptr_t>(rows) % 16)
+    return hipErrorInvalidValue;
+  static_assert(SENTIO_MMR_MAX_C == MMR_CMAX, "limit of the header");
+  auto kern = scales == nullptr ? mmr_select_kernel<true>
+                                : mmr_select_kernel<false>;
+  hipError_t e = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(kern),
+      hipFuncAttributeMaxDynamicSharedMemorySize, MMR_LDS);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(IDX_WAVES * WAVE), MMR_LDS,
+                     stream, (const char*)rows, scales, (const _Float16*)q,
+                     cand, out_s, out_r, N, D, C, k, lam, 1.f - lam);
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
 
 hipError_t sentio_bm25_topk_plan(long N, int* blocks, int* tile_docs,
                                  int* cap) {

@@ -169,6 +169,23 @@ hipError_t sentio_cosine_topk_masked(const void* q, const void* rows,
                                      float* out_s, long* out_r, long N, int D,
                                      int B, int k, int blocks,
                                      hipStream_t stream);
+// MMR over a candidate list, one block per query: q fp16 [B, D]; rows as in
+// sentio_cosine_topk_masked (e4m3fn codes with scales, or fp16 when scales
+// is null); cand int64 [B, C], index rows, unique within a list, -1 padding
+// at the tail (a row outside [0, N) counts as padding).  Step t picks the
+// unpicked valid candidate with the largest lam * (x_i . q) - (1 - lam) *
+// max over the picks p of (x_i . x_p), a tie to the lower position in cand;
+// all dot products are fp32 sums over the stored values.  out_s f32 [B, k]:
+// x_p . q of each pick, out_r i64 [B, k]: its index row, in pick order,
+// (-inf, -1) past the valid candidates; deterministic.  dims are (N, D, B,
+// C, k).  hipErrorInvalidValue unless D % 32 == 0, 32 <= D <= 1024, 1 <= C
+// <= 128, 1 <= k <= C, 0 <= lam <= 1, N < 2^31 and q and rows are 16-byte
+// aligned
+#define SENTIO_MMR_MAX_C 128
+hipError_t sentio_mmr_select(const void* q, const void* rows,
+                             const float* scales, const long* cand,
+                             float* out_s, long* out_r, long N, int D, int B,
+                             int C, int k, float lam, hipStream_t stream);
 hipError_t sentio_bm25(const long* term_ids, const long* qoff,
                        const long* starts, const int* post_doc,
                        const float* post_tf, const float* idf,

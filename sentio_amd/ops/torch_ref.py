@@ -256,6 +256,46 @@ def cosine_topk_masked(
     return vals, idx.masked_fill(pad, -1)
 
 
+def mmr_select(
+    q: torch.Tensor, rows: torch.Tensor, scales: torch.Tensor | None,
+    cand: torch.Tensor, k: int, lam: float,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The MMR selection's spec.  q [B, D]; rows: e4m3fn codes with scales
+    (a row's value is code * scale) or, with scales None, plain rows; cand
+    int64 [B, C]: index rows, unique within a list, -1 padding at the tail.
+    With rel_i = x_i . q and S_ij = x_i . x_j in fp32, step t picks the
+    unpicked valid candidate with the largest lam * rel_i - (1 - lam) *
+    red_i, a tie to the lower position; red_i is 0 before the first pick and
+    max(red_i, S_ip) after a pick p.  Returns (rel of the picks f32 [B, k],
+    their index rows i64 [B, k]) in pick order, padded with (-inf, -1) past
+    the valid candidates.  Tensor ops only: no host sync on a GPU."""
+    B, C = cand.shape
+    valid = cand >= 0
+    x = rows[cand.clamp_min(0).reshape(-1)]
+    x = x.float() if scales is None else \
+        x.view(torch.float8_e4m3fn).float() \
+        * scales[cand.clamp_min(0).reshape(-1)].float().unsqueeze(1)
+    x = x.view(B, C, -1)
+    rel = torch.bmm(x, q.float().unsqueeze(2)).squeeze(2)
+    S = torch.bmm(x, x.transpose(1, 2))
+    red = torch.zeros_like(rel)
+    closed = ~valid
+    out_s = rel.new_full((B, k), float("-inf"))
+    out_r = cand.new_full((B, k), -1)
+    floor = torch.finfo(torch.float32).min
+    for t in range(k):
+        obj = (lam * rel - (1.0 - lam) * red).clamp_min(floor) \
+            .masked_fill(closed, float("-inf"))
+        p = obj.argmax(dim=1, keepdim=True)         # the first of equal maxima
+        ok = ~closed.gather(1, p)
+        out_s[:, t:t + 1] = torch.where(ok, rel.gather(1, p), out_s[:, t:t + 1])
+        out_r[:, t:t + 1] = torch.where(ok, cand.gather(1, p), out_r[:, t:t + 1])
+        closed = closed.scatter(1, p, True)
+        red = torch.maximum(red, S.gather(2, p.unsqueeze(1).expand(B, C, 1))
+                            .squeeze(2))
+    return out_s, out_r
+
+
 def bm25_score(
     term_ids: torch.Tensor,
     indptr: torch.Tensor,

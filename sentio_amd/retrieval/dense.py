@@ -18,18 +18,33 @@ def _doc_text(doc: Document) -> str:
 
 
 class DenseRetriever(BaseRetriever):
-    def __init__(self, embedder, index: DenseIndex):
+    def __init__(self, embedder, index: DenseIndex,
+                 mmr_lambda: float | None = None,
+                 mmr_fetch_k: int | None = None):
         self.embedder = embedder
         self.index = index
+        self.mmr_lambda = mmr_lambda
+        self.mmr_fetch_k = mmr_fetch_k
 
     def retrieve(self, query: str, top_k: int = 10,
-                 metadata_filter: dict | None = None) -> list[Document]:
+                 metadata_filter: dict | None = None,
+                 *, mmr_lambda: float | None = None) -> list[Document]:
         """metadata_filter: equality conditions on document metadata; exact
-        with a DENSE_FILTER=exact index, a post-filter otherwise."""
+        with a DENSE_FILTER=exact index, a post-filter otherwise.
+        mmr_lambda: overrides the retriever's default (DENSE_MMR_LAMBDA) for
+        this call; when either is set the hits are diversified by maximal
+        marginal relevance (DenseIndex.search) and carry metadata["mmr_rank"],
+        their place in pick order; "score" stays the cosine."""
         qv = self.embedder.embed([query])
-        hits = self.index.search(qv, top_k, metadata_filter)[0]
+        lam = self.mmr_lambda if mmr_lambda is None else mmr_lambda
+        if lam is None:
+            hits = self.index.search(qv, top_k, metadata_filter)[0]
+        else:
+            hits = self.index.search(qv, top_k, metadata_filter,
+                                     mmr_lambda=lam,
+                                     fetch_k=self.mmr_fetch_k)[0]
         out: list[Document] = []
-        for doc_id, score in hits:
+        for rank, (doc_id, score) in enumerate(hits):
             src = self.index.get_document(doc_id)
             if src is None:
                 continue
@@ -37,5 +52,7 @@ class DenseRetriever(BaseRetriever):
             doc.metadata["score"] = float(score)
             doc.metadata["dense_score"] = float(score)
             doc.metadata["retrieval_method"] = "dense"
+            if lam is not None:
+                doc.metadata["mmr_rank"] = rank
             out.append(doc)
         return out

@@ -24,7 +24,9 @@ def create_retriever(
     scorer_plugins: list | None = None,
 ):
     strategy = settings.retrieval_strategy
-    dense = DenseRetriever(embedder, dense_index)
+    dense = DenseRetriever(embedder, dense_index,
+                           mmr_lambda=settings.dense_mmr_lambda,
+                           mmr_fetch_k=settings.dense_mmr_fetch_k)
     sparse = BM25Retriever(bm25_index, doc_lookup=dense_index.get_document,
                            device=device)
     if strategy == "dense":
